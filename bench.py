@@ -13,7 +13,10 @@ straight into the gather's device buffer) and is gathered on rank 0 over RCCL wh
 of every rank where it arrives.  Two site sets are measured: 600 000 sites (every donor sequence carries one) and BASELINE config 5's
 literal 100 000.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` and `cpu_baseline`.
+A plain run sets up, warms up, times --steps steps in one block, writes the last step's results with --dump-outputs DIR, and prints ONE
+JSON line (rank 0) with the driver's contract.  --full adds everything else the benchmark measures or checks: repeated timed blocks (the
+median is reported), the results against the truth, `roofline` (kernels alone, random-read ceiling), the input-side and tool secondaries,
+`cpu_baseline`, the secondary workloads and BASELINE config 5's literal site set.
 """
 import argparse
 import hashlib
@@ -49,7 +52,9 @@ def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="GPUs of the job (default: WORLD_SIZE, else 1).  N > 1 without WORLD_SIZE in the environment: this process starts the N ranks itself (torch.distributed.run)")
     ap.add_argument("--full-line", action="store_true", help="print the whole detail object as the last line instead of the compact one (what the child processes of the secondary workloads hand to their parent)")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="where the whole detail object is written (the last stdout line is the compact one)")
+    ap.add_argument("--detail", default=None, help="where the whole detail object is written (the last stdout line is the compact one); default with --full: bench_detail.json, else none")
+    ap.add_argument("--full", action="store_true", help="measure and check everything besides the headline (see the module's docstring); off: set-up, warm-up, the timed steps, --dump-outputs, the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step returned (records and a fixed sample of the sequences) as DIR/<name>.npy, float64 / float32")
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--workload", default=os.environ.get("MTG_BENCH_WORKLOAD", "human"), choices=list(WORKLOADS))
@@ -61,7 +66,7 @@ def parse():
     ap.add_argument("--nseq", type=int, default=0)
     ap.add_argument("--scaling", default="auto", choices=["auto", "weak", "strong"], help="N > 1: strong (default) = one fixed site set sharded over the ranks; weak = one batch per rank and step")
     ap.add_argument("--strong-sites", type=int, default=0, help="size of the sharded site set (default: two measurements, 600000 = every donor sequence carries a site, and BASELINE config 5's 100000)")
-    ap.add_argument("--repeats", type=int, default=0, help="timed blocks of --steps steps (0: at least 5 and at least ~1 s of timed work); the median block is reported")
+    ap.add_argument("--repeats", type=int, default=0, help="timed blocks of --steps steps (0: one block; with --full at least 5 and at least ~1 s of timed work); the median block is reported")
     ap.add_argument("--cpu-sites", type=int, default=30000, help="sites of the bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-index-seqs", type=int, default=30000, help="donor sequences in the CPU baseline's index")
     ap.add_argument("--host-threads", type=int, default=-1, help="host threads per rank for the per-gap passes (default: the library's pool = CPU budget of the process, shared between the ranks)")
@@ -71,11 +76,94 @@ def parse():
     ap.add_argument("--no-ceiling", action="store_true", help="skip the random-line ceiling micro-benchmark")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (host-string input, sequences left in HBM, the tool, the other workloads)")
     ap.add_argument("--no-tool", action="store_true", help="skip the tool measurement (MindTheGap fill on the batches' sites)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.full and a.detail is None:
+        a.detail = os.path.join(ROOT, "bench_detail.json")
+    return a
 
 
 def rc(s):
     return s[::-1].translate(str.maketrans("ACGT", "TGCA"))
+
+
+def site_triples(S, s0, s1, chunk=8192):
+    """[S.site(i) for i in range(s0, s1)] -- (left k-mer, right k-mer, inserted sequence) -- decoded from the packed donor a chunk of sites
+    at a time: S.site decodes the whole sequence of every site, which was most of the set-up of a run"""
+    from mindthegap_amd.synth import NT
+    k, out = S.k, []
+    for c0 in range(s0, s1, chunk):
+        ii = np.arange(c0, min(s1, c0 + chunk))
+        p, L = S.pos[ii].astype(np.int64), S.ins_len[ii].astype(np.int64)
+        n = L + 2 * k  # nucleotides p - k .. p + L + k of donor sequence i
+        start = np.cumsum(n) - n
+        q = np.arange(int(n.sum()), dtype=np.int64) + np.repeat(p - k - start, n)
+        w = S.words[np.repeat(ii, n), q >> 5]
+        txt = NT[((w >> (2 * (q & 31)).astype(np.uint64)) & np.uint64(3)).astype(np.uint8)].tobytes().decode()
+        for j in range(len(ii)):
+            a0, l = int(start[j]), int(L[j])
+            out.append((txt[a0:a0 + k], txt[a0 + k + l:a0 + 2 * k + l], txt[a0 + k:a0 + k + l]))
+    return out
+
+
+DUMP_LIMIT = 64 << 20     # bytes of all the .npy files of --dump-outputs together
+DUMP_MAX_GAPS = 200000    # gap rows; a larger step is written as a fixed, seeded sample of its gaps
+DUMP_SEQ_SAMPLE = 2048    # filled sequences written nucleotide by nucleotide (a fixed, seeded sample; every one's length and hash are in filled_records)
+DUMP_SEQ_NT = 4 << 20     # at most this many nucleotides in the sample
+
+
+def _hash48(b):
+    """48 bits of a digest: exact in a float64"""
+    return float(int.from_bytes(hashlib.blake2b(b, digest_size=6).digest(), "little"))
+
+
+def dump_outputs(lib, kept, out_dir):
+    """--dump-outputs: the result sets of the last timed step -- kept = [(batch, forward results, reverse results or None, gaps the reverse
+    attempt took)] -- as a caller of the fill receives them, written as out_dir/<name>.npy:
+      gap_records     float64 (gaps, 12): batch, gap, reverse attempt, nb_nodes, total_nt, nb_terminal, has_solution_counts, nb_total_filled,
+                      nb_reported, n_filled, length and 48-bit hash of the extension
+      filled_records  float64 (sequences, 11): gap_records row, rank in the gap, nb_errors_in_anchor, target_index, avg_coverage,
+                      median_coverage, qual, solution_count, solution_rank, length and 48-bit hash of the sequence
+      seq_sample      float32: the nucleotides (A C G T = 0 1 2 3, other 4) of a fixed, seeded sample of the sequences, one after the other
+      seq_sample_index float64 (sample, 3): filled_records row, offset in seq_sample, length
+    Returns {name: bytes written}."""
+    rows = []  # (batch, gap, reverse, results handle, index in the results)
+    for b, h, h2, unfilled in sorted(kept, key=lambda e: e[0].gidx):
+        rows += [(b.gidx, i, 0, h, i) for i in range(b.n)]
+        if h2 is not None:
+            rows += [(b.gidx, int(g), 1, h2, j) for j, g in enumerate(unfilled)]
+    if len(rows) > DUMP_MAX_GAPS:
+        rows = [rows[i] for i in np.sort(np.random.default_rng(12345).choice(len(rows), DUMP_MAX_GAPS, replace=False))]
+    gap_rec, fill_rec, seqs = [], [], []
+    for (gidx, gi, rev, h, i) in rows:
+        r = lib.mtg_results_get(h, i).contents
+        ext = r.extension or b""
+        for j in range(r.n_filled):
+            f = r.filled[j]
+            s = f.seq or b""
+            fill_rec.append((len(gap_rec), j, f.nb_errors_in_anchor, f.target_index, f.avg_coverage, f.median_coverage, f.qual, f.solution_count, f.solution_rank, len(s), _hash48(s)))
+            seqs.append(s)
+        gap_rec.append((gidx, gi, rev, r.nb_nodes, r.total_nt, r.nb_terminal, r.has_solution_counts, r.nb_total_filled, r.nb_reported, r.n_filled, len(ext), _hash48(ext)))
+    arrays = {"gap_records": np.array(gap_rec, dtype=np.float64).reshape(-1, 12), "filled_records": np.array(fill_rec, dtype=np.float64).reshape(-1, 11)}
+    pick = np.sort(np.random.default_rng(54321).choice(len(seqs), min(DUMP_SEQ_SAMPLE, len(seqs)), replace=False)) if seqs else np.zeros(0, dtype=np.int64)
+    code = np.full(256, 4, dtype=np.uint8)
+    code[np.frombuffer(b"ACGT", dtype=np.uint8)] = np.arange(4, dtype=np.uint8)
+    parts, index, off = [], [], 0
+    for j in pick:
+        s = seqs[j][: max(DUMP_SEQ_NT - off, 0)]
+        parts.append(code[np.frombuffer(s, dtype=np.uint8)])
+        index.append((j, off, len(s)))
+        off += len(s)
+    arrays["seq_sample"] = (np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)).astype(np.float32)
+    arrays["seq_sample_index"] = np.array(index, dtype=np.float64).reshape(-1, 3)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs, more than %d" % (total, DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return {name: int(v.nbytes) for name, v in arrays.items()}
 
 
 def reference_binary():
@@ -123,6 +211,7 @@ def _num(x, digits=4):
     return float("%.*g" % (digits, x))
 
 
+SETTLE_S = 0.5  # seconds of untimed steps at the end of the set-up, before the warm-up steps (see measure)
 COMPACT_LIMIT = 6000  # bytes: what the driver's tail of stdout holds with room to spare (round 4's 24 KB line was not parsed)
 
 
@@ -278,7 +367,7 @@ def main():
     configs = []
     if scaling == "strong":
         big = min(nloci0, 6 * batch_sites)
-        sets = [a.strong_sites] if a.strong_sites else [big] + ([batch_sites] if big != batch_sites else [])
+        sets = [a.strong_sites] if a.strong_sites else [big] + ([batch_sites] if big != batch_sites and a.full else [])
         for total_sites in sets:
             # global batch index = position of the batch in site order: rank r's batches follow those of the ranks before it (shard.py: strong_plan,
             # exercised at world sizes 2 and 8 by tests/test_distributed_cpu.py)
@@ -334,8 +423,7 @@ def main():
             b = B()
             b.gidx = gidx
             b.gaps, b.expected = [], []
-            for i in range(s0, s1):
-                l, r, ins = S.site(i)
+            for i, (l, r, ins) in zip(range(s0, s1), site_triples(S, s0, s1)):
                 b.gaps.append(mtg.Gap(l, r, [(r, S.site_name(i), False)]))
                 b.expected.append(ins)
             b.strings = mtg.Index.prepare_gaps(b.gaps)
@@ -344,7 +432,7 @@ def main():
             b.n = s1 - s0
             b.s0 = s0
             batches.append(b)
-        st = dict(pg=None, hbm_pool=None, seen={}, bad=[], keep=None)
+        st = dict(pg=None, hbm_pool=None, seen={}, bad=[], keep=None, kept=[])
         full_wire_check = os.environ.get("MTG_BENCH_WIRE_CHECK", "") == "full"
         rotate = cfg["rotate"]
 
@@ -364,11 +452,11 @@ def main():
                 if st["keep"] is not None:
                     st["keep"][tag] = t.cpu().numpy().copy()
 
-        def fill(b, prepared=None, want_seqs=False, record=False):
+        def fill(b, prepared=None, want_seqs=False, record=False, keep=None):
             """one batch: forward attempt for every site, reverse attempt (src/Filler.cpp:669-680) for the unfilled ones.  The results are
             host records and ASCII sequences when the call returns.  N > 1: the batch also leaves in relocatable form -- records and
             sequences, tagged with its global batch index -- written by the result kernel into the gather's device buffer, and is gathered
-            on rank 0 over RCCL / xGMI while the next batches run."""
+            on rank 0 over RCCL / xGMI while the next batches run.  keep (a list): the result sets are appended to it instead of freed."""
             prepared = b.prepared if prepared is None else prepared
             seqs = None
             pg = st["pg"]
@@ -389,14 +477,17 @@ def main():
             else:
                 h, nf, seqs = idx.fill_prepared(prepared, params, want_seqs=want_seqs)
             stt = mtg.last_batch_stats()
-            idx.free_results(h)
+            if keep is None:
+                idx.free_results(h)
             unfilled = np.nonzero(nf == 0)[0]
             n_filled = int((nf > 0).sum())
+            h2 = None
             if len(unfilled):
                 rg = [mtg.Gap(rc(b.gaps[j].target), rc(b.gaps[j].source), [(rc(b.gaps[j].source), "rev", False)], reverse=True) for j in unfilled]
                 h2, nf2, _ = idx.fill_prepared(mtg.Index.prepare_gaps(rg), params, want_seqs=False)
                 st2 = mtg.last_batch_stats()
-                idx.free_results(h2)
+                if keep is None:
+                    idx.free_results(h2)
                 n_filled += int((nf2 > 0).sum())
                 for key in acc:
                     if key in st2:
@@ -407,7 +498,16 @@ def main():
                         if key in stt:
                             acc[key] += stt[key]
                     acc["gaps"] += b.n
+            if keep is not None:
+                keep.append((b, h, h2, unfilled))
             return n_filled, seqs
+
+        def release(kept):
+            for (_b, h, h2, _u) in kept:
+                idx.free_results(h)
+                if h2 is not None:
+                    idx.free_results(h2)
+            del kept[:]
 
         def pad_gathers(count):
             """a rank with fewer batches than the others sends empty payloads, so that every rank issues the same number of collectives"""
@@ -461,13 +561,16 @@ def main():
             if errs:
                 raise errs[0]
 
-        def run_block(count, record, first_step=0, host_strings=False, host_text=False):
+        def run_block(count, record, first_step=0, host_strings=False, host_text=False, keep=None):
             """`count` steps, a.in_flight batches in flight: the caller threads take the next batch off a shared queue, like the reference's
-            Dispatcher threads take the next group of records; every batch is complete when this returns"""
+            Dispatcher threads take the next group of records; every batch is complete when this returns.  keep: the result sets of the
+            block's last step are appended to it (fill)"""
             work = []
             for s in range(first_step, first_step + count):
                 work += [batches[s % len(batches)]] if rotate else list(batches)
-            run_tasks([(lambda b: fill(b, prepared=b.strings if host_strings else b.text if host_text else None, record=record), (b,)) for b in work])
+            last = len(work) - (1 if rotate else len(batches))  # the first batch of the last step
+            run_tasks([(lambda b, kp: fill(b, prepared=b.strings if host_strings else b.text if host_text else None, record=record, keep=kp), (b, keep if j >= last else None))
+                       for j, b in enumerate(work)])
             if st["pg"] is not None and not rotate:
                 pad_gathers(count * (cfg["max_per_rank"] - len(batches)))
 
@@ -486,6 +589,11 @@ def main():
                 t.start()
             for t in ts:
                 t.join()
+            # the rest of the set-up: steps for SETTLE_S seconds, until the device and the caller threads run as they do in the steady state.
+            # Without it, a block timed right after a few warm-up steps ran at 1.02-1.07 ms per step against 0.75 for every later block
+            t_end = time.perf_counter() + SETTLE_S
+            while time.perf_counter() < t_end:
+                run_block(max(1, 4 * a.in_flight) if rotate else 1, False)
         if dist_on:
             # a payload holds records (80 bytes per gap) and sequences; the capacity is agreed on (the gather moves whole buffers)
             need = max([0] + [sum(len(e) + 1 for e in b.expected) + 96 * b.n + 4096 for b in batches])
@@ -503,10 +611,15 @@ def main():
             st["gather_slots"] = slots
         run_block(a.warmup, False)
 
-        def timed_block(first_step):
+        dump = bool(a.dump_outputs) and rank == 0
+
+        def timed_block():
+            """a.steps steps; every block fills the same batches in the same order, so that the blocks are alike and the last step (whose
+            result sets --dump-outputs keeps) is the same batch whatever the number of blocks"""
+            keep = [] if dump else None
             barrier()
             t0 = time.perf_counter()
-            run_block(a.steps, True, first_step)
+            run_block(a.steps, True, 0, keep=keep)
             if st["pg"] is not None:
                 st["pg"].drain()  # the gathers still in flight belong to the timed steps
             barrier()
@@ -515,18 +628,24 @@ def main():
                 tt = torch.tensor([el], device=cdev, dtype=torch.float64)
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
                 el = float(tt.item())
+            if keep is not None:
+                release(st["kept"])
+                st["kept"] = keep
             return el
 
-        times = [timed_block(0)]
-        repeats = a.repeats if a.repeats > 0 else int(min(60, max(5, np.ceil(1.0 / max(times[0], 1e-6)))))
+        times = [timed_block()]
+        repeats = a.repeats if a.repeats > 0 else int(min(60, max(5, np.ceil(1.0 / max(times[0], 1e-6))))) if a.full else 1
         if dist_on:  # every rank must run the same number of blocks
             rt = torch.tensor([repeats], device=cdev, dtype=torch.int64)
             dist.broadcast(rt, src=0)
             repeats = int(rt.item())
         for r in range(1, repeats):
-            times.append(timed_block(r * a.steps))
+            times.append(timed_block())
         elapsed = float(np.median(times))
         n_arrived_timed = len(st["seen"])
+        if not a.full:  # a plain run: the timed steps are all it does on the device
+            pg_saved, st["pg"] = st["pg"], None
+            return dict(acc=acc, batches=batches, st=st, pg=pg_saved, times=times, elapsed=elapsed, kept=st["kept"], release=release, value=cfg["step_sites"] * a.steps / elapsed)
 
         # ---------------------------------------------------------------- verification (untimed)
         # (1) N > 1: one more step whose payloads rank 0 brings to the host: EVERY batch of EVERY rank is rebuilt from its payload
@@ -599,7 +718,7 @@ def main():
             """the caller threads of this configuration leave (one sentinel each); the report's later measurements start their own through run_tasks no more"""
             for _ in callers:
                 tasks.put(None)
-        return dict(acc=acc, batches=batches, st=st, pg=pg_saved, times=times, elapsed=elapsed, gathered=gathered, identical=identical, st_alone=st_alone, stop_callers=stop_callers,
+        return dict(acc=acc, batches=batches, st=st, pg=pg_saved, times=times, elapsed=elapsed, kept=st["kept"], release=release, gathered=gathered, identical=identical, st_alone=st_alone, stop_callers=stop_callers,
                     n_filled=n_filled_all, n_sites=n_sites_all, fill=fill, run_block=run_block, run_tasks=run_tasks, value=cfg["step_sites"] * a.steps / elapsed)
 
     results = []
@@ -613,18 +732,41 @@ def main():
                 results[-1]["pg"] = None
             torch.cuda.empty_cache()
         results.append(measure(c))
+        if ci == 0 and results[0]["kept"]:  # --dump-outputs, rank 0: what the headline's last timed step returned
+            dump_outputs(lib, results[0]["kept"], a.dump_outputs)
+            results[0]["release"](results[0]["kept"])
     R0, cfg0 = results[0], configs[0]
-    if rank != 0:
+
+    def close_dist():
         if dist_on:
             for r in results:
                 if r["pg"] is not None:
                     r["pg"].drain()
             dist.destroy_process_group()
+
+    if rank != 0:
+        close_dist()
         return
 
-    acc, batches, times, elapsed, value, st_alone = R0["acc"], R0["batches"], R0["times"], R0["elapsed"], R0["value"], R0["st_alone"]
+    acc, batches, times, elapsed, value = R0["acc"], R0["batches"], R0["times"], R0["elapsed"], R0["value"]
     step_sites = cfg0["step_sites"]
     sites_per_rank_step = sum(b.n for b in batches) if not cfg0["rotate"] else batch_sites
+    out = {"metric": "breakpoints filled/sec", "value": value, "unit": "breakpoints/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+           "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": scaling if world > 1 else "none", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+           "config": {"workload": desc, "sites_per_step": step_sites, "sites_per_batch": batch_sites, "sites_per_rank_and_step": sites_per_rank_step, "distinct_batches_per_rank": len(batches),
+                      "site_set": cfg0["total"], "donor_sequences": S.nseq, "erroneous_fragments": int(len(S.extra_lens)), "k": k, "max_nodes": 100, "max_length": 10000,
+                      "index": "exact k-mer set of the donor, abundance of a k-mer = Poisson(24) drawn from its hash, at least 3 (SURVEY 8d; no reads simulated)", "nb_solid_kmers": int(info["nb_solid_kmers"]),
+                      "nb_unitigs": int(info["nb_unitigs"]), "index_bytes": int(info["device_bytes"]), "unitig_store_bytes": int(info["unitig_bytes"]), "index_build_s": t_index,
+                      "genome_gen_s": t_gen, "donor_upload_s": t_donor_up, "batches_in_flight": a.in_flight, "input": "host strings, marshalled in every step" if a.host_strings else "prepared batches, resident in HBM",
+                      "output": "C-ABI records + ASCII sequences in page-locked host memory" + ("; every batch also gathered on rank 0 in relocatable form (records + sequences), validated there" if dist_on else "")},
+           "timed_blocks": {"blocks": len(times), "steps_per_block": a.steps, "reported": "median", "ms_per_step_min": min(times) / a.steps * 1e3,
+                            "ms_per_step_median": elapsed / a.steps * 1e3, "ms_per_step_max": max(times) / a.steps * 1e3, "timed_seconds_total": sum(times)}}
+    if not a.full:
+        close_dist()
+        emit(a, out)
+        return
+
+    st_alone = R0["st_alone"]
     secondary = {}
     if len(results) > 1:  # BASELINE config 5 literally: the 100 000-site set sharded over the ranks
         R1, c1 = results[1], configs[1]
@@ -1045,24 +1187,14 @@ def main():
         index_build["traffic"] = {kn.split("::")[-1]: kv.get("hbm_bytes_per_launch") for kn, kv in pb.get("kernels", {}).items()}
         index_build["traffic_is"] = "REPLAYED from %s (rocprofv3 --pmc passes of scripts/r4_build.py, HEAD %s); FETCH_SIZE x2 applied to no kernel (16 B/lane table scans, scattered buckets)" % (os.path.relpath(pmcb, ROOT), pb.get("head", "?"))
 
-    out = {"metric": "breakpoints filled/sec", "value": value, "unit": "breakpoints/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-           "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": scaling if world > 1 else "none", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-           "config": {"workload": desc, "sites_per_step": step_sites, "sites_per_batch": batch_sites, "sites_per_rank_and_step": sites_per_rank_step, "distinct_batches_per_rank": len(batches),
-                      "site_set": cfg0["total"], "donor_sequences": S.nseq, "erroneous_fragments": int(len(S.extra_lens)), "k": k, "max_nodes": 100, "max_length": 10000,
-                      "index": "exact k-mer set of the donor, abundance of a k-mer = Poisson(24) drawn from its hash, at least 3 (SURVEY 8d; no reads simulated)", "nb_solid_kmers": int(info["nb_solid_kmers"]),
-                      "nb_unitigs": int(info["nb_unitigs"]), "index_bytes": int(info["device_bytes"]), "unitig_store_bytes": int(info["unitig_bytes"]), "index_build_s": t_index,
-                      "genome_gen_s": t_gen, "donor_upload_s": t_donor_up, "batches_in_flight": a.in_flight, "input": "host strings, marshalled in every step" if a.host_strings else "prepared batches, resident in HBM",
-                      "output": "C-ABI records + ASCII sequences in page-locked host memory" + ("; every batch also gathered on rank 0 in relocatable form (records + sequences), validated there" if dist_on else "")},
-           "timed_blocks": {"blocks": len(times), "steps_per_block": a.steps, "reported": "median", "ms_per_step_min": min(times) / a.steps * 1e3,
-                            "ms_per_step_median": elapsed / a.steps * 1e3, "ms_per_step_max": max(times) / a.steps * 1e3, "timed_seconds_total": sum(times)},
-           "filled": R0["n_filled"], "sites_verified": R0["n_sites"] if R0["identical"] is not None else None, "sites_run_in_the_untimed_pass": R0["n_sites"],
+    out.update({"filled": R0["n_filled"], "sites_verified": R0["n_sites"] if R0["identical"] is not None else None, "sites_run_in_the_untimed_pass": R0["n_sites"],
            "filled_per_s": value * R0["n_filled"] / max(R0["n_sites"], 1),
            "filled_sequences_identical_to_truth": R0["identical"], "gathered_payload_verified": R0["gathered"],
            "stage_ms_per_batch": {"k_stage_a+k_finish": acc["kernel_ms"] / Ln, "k_finish": acc["finish_kernel_ms"] / Ln, "parked_gaps": acc["n_parked_gaps"] / Ln, "lean_gaps": acc["n_lean_gaps"] / Ln, "event_gap_before_k_copy": acc["lean_kernel_ms"] / Ln, "k_copy": (acc["copy_kernel_ms"] - acc["lean_kernel_ms"]) / Ln,
                                   "k_post+scans": acc["post_kernel_ms"] / Ln, "k_emit": acc["emit_kernel_ms"] / Ln, "d2h": acc["d2h_ms"] / Ln,
                                   "host": acc["host_ms"] / Ln, "c_call": acc["total_ms"] / Ln, "first_kernel_to_last": acc["device_span_ms"] / Ln,
                                   "note": "kernel columns are 0 unless KERNEL_TIMERS is set: the timed blocks record three events per batch; roofline.one_batch_alone_ms has every kernel's own time"},
-           "roofline": roof, "cpu_baseline": cpu, "index_build": index_build}
+           "roofline": roof, "cpu_baseline": cpu, "index_build": index_build})
     out.update(secondary)
     # ---------------------------------------------------------------- secondary lines: the workloads whose walks cross bubbles (SNPs; indels; tips and error bubbles), each
     # as a child process once this one has given the device back (two human-scale indexes do not fit the HBM together)
@@ -1077,7 +1209,7 @@ def main():
             try:
                 # every child checks a sample of its sites against the oracle (cpu_baseline leg: 6 000 sites, index over the donor sequences of those loci): the
                 # alleles and error bubbles of these sets have no closed-form truth, the oracle's fills are the reference
-                cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", wl, "--batches", "3", "--cpu-sites", "6000", "--cpu-index-seqs", "12000", "--cpu-same-sites", "0",
+                cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--workload", wl, "--batches", "3", "--cpu-sites", "6000", "--cpu-index-seqs", "12000", "--cpu-same-sites", "0",
                                      "--no-ceiling", "--no-secondary", "--full-line", "--detail", "", "--steps", str(a.steps), "--warmup", str(a.warmup), "--in-flight", str(a.in_flight), "--repeats", "5"],
                                     capture_output=True, text=True, timeout=600)
                 d = json.loads(cp.stdout.strip().splitlines()[-1])
@@ -1121,11 +1253,12 @@ def main():
                     out[key] = json.loads([l for l in cp.stdout.splitlines() if l.startswith("{")][-1])
                 except Exception as e:
                     out[key] = {"error": repr(e)[:300]}
-    if dist_on:
-        for r in results:
-            if r["pg"] is not None:
-                r["pg"].drain()
-        dist.destroy_process_group()
+    close_dist()
+    emit(a, out)
+
+
+def emit(a, out):
+    """rank 0's output: the detail object to --detail and stderr, then the compact line (--full-line: the detail object) as the last stdout line"""
     # the JSON line is the last thing on stdout: whatever native libraries (RCCL's version banner) left in the C stdio buffer goes first
     sys.stdout.flush()
     try:
@@ -1141,9 +1274,6 @@ def main():
         try:
             with open(detail_path, "w") as f:
                 json.dump(out, f, indent=1)
-            side = os.path.join(ROOT, "gpurun_out")  # scratch that travels back from the GPU box
-            if os.path.isdir(side):
-                shutil.copyfile(detail_path, os.path.join(side, os.path.basename(detail_path)))
         except OSError as e:
             print("bench.py: detail file not written: %r" % (e,), file=sys.stderr)
             detail_path = None

@@ -4,7 +4,7 @@ for cfg in "2 0.5" "2 0.35" "4 0.5" "4 0.35" "8 0.5"; do
   set -- $cfg
   make -C mindthegap_amd/csrc -B EXTRA="-DMTG_ADJ_SLOTS=$1" > /dev/null 2>&1
   echo "=== ADJ_SLOTS=$1 load=$2"
-  MTG_INDEX_LOAD=$2 timeout 600 python bench.py --steps 3 --warmup 1 --cpu-sites 0 --no-ceiling 2>&1 | tail -1 | python3 -c "
+  MTG_INDEX_LOAD=$2 timeout 600 python bench.py --full --steps 3 --warmup 1 --cpu-sites 0 --no-ceiling 2>&1 | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 r=d['roofline']; c=d['config']

@@ -8,7 +8,7 @@ for v in ${VARIANTS:-0 2}; do
   python3 scripts/diag_batches.py 2 2>&1 | grep "^batch" | cut -c1-100
   HET=1 python3 scripts/diag_batches.py 1 2>&1 | grep "^batch" | cut -c1-100
   for w in human human-het; do
-    timeout 300 python bench.py --cpu-sites 0 --no-ceiling --no-secondary --workload $w 2>/dev/null | python3 -c "
+    timeout 300 python bench.py --full --cpu-sites 0 --no-ceiling --no-secondary --workload $w 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$w', 'value %.4g ms/step %.3f'%(d['value'], d['ms_per_step']), {k:round(v,3) for k,v in d['stage_ms_per_batch'].items()})"
   done

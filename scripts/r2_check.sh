@@ -5,7 +5,7 @@ timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; tail -2 $
 python3 scripts/diag_batches.py 4 2>&1 | grep -v amdgpu.ids | grep "^batch" | cut -c1-150
 HET=1 python3 scripts/diag_batches.py 2 2>&1 | grep -v amdgpu.ids | grep "^batch" | cut -c1-150
 for w in human human-het; do
-  timeout 300 python bench.py --cpu-sites 0 --no-ceiling --no-secondary --workload $w > $O/b_$w.json 2> $O/b_$w.err
+  timeout 300 python bench.py --full --cpu-sites 0 --no-ceiling --no-secondary --workload $w > $O/b_$w.json 2> $O/b_$w.err
   python3 - $O/b_$w.json <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1]))

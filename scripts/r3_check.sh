@@ -4,7 +4,7 @@ out=gpurun_out/${1:-r3_check}
 mkdir -p $out
 timeout 700 python -u -m pytest tests/test_gpu_parity.py tests/test_micro_cases.py -m gpu -x -q -p no:cacheprovider 2>&1 | grep -E "passed|failed|Error|assert|^tests/" | tail -n 15 > $out/pytest.txt; cat $out/pytest.txt
 timeout ${2:-1200} python -u -m pytest tests/test_gpu_fullsize.py -m gpu -x -q -s -p no:cacheprovider 2>&1 | grep -E "passed|failed|Error|assert|^tests/|human-scale index|config 4" | tail -n 15 > $out/pytest_full.txt; cat $out/pytest_full.txt
-timeout 600 python bench.py --no-secondary --cpu-sites 0 --steps 20 --warmup 5 > $out/bench_human.json 2> $out/bench_human.err
+timeout 600 python bench.py --full --no-secondary --cpu-sites 0 --steps 20 --warmup 5 > $out/bench_human.json 2> $out/bench_human.err
 python - $out/bench_human.json <<'PY'
 import json,sys
 try:

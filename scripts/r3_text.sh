@@ -4,7 +4,7 @@ out=gpurun_out/${1:-r3_text}; mkdir -p $out
 timeout 900 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -q -p no:cacheprovider -k "text or cli or reverse or replica or edge" 2>&1 | grep -E "passed|failed|Error|assert|^tests/" | tail -n 15 | tee $out/pytest.txt
 for th in 2 0; do
   export MTG_POOL_THREADS=$th; [ $th = 0 ] && unset MTG_POOL_THREADS
-  MTG_TOOL_TIMERS=1 timeout 900 python bench.py --no-children --no-ceiling --cpu-sites 0 --steps 20 --warmup 5 > $out/bench_th$th.json 2> $out/bench_th$th.err
+  MTG_TOOL_TIMERS=1 timeout 900 python bench.py --full --no-children --no-ceiling --cpu-sites 0 --steps 20 --warmup 5 > $out/bench_th$th.json 2> $out/bench_th$th.err
   grep "\[tool\]" $out/bench_th$th.err | tail -n 2
   python - $out/bench_th$th.json $th <<'PY'
 import json,sys

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the headline workload without its secondary measurements: value, the kernels of one batch alone, left-in-HBM rate.  gpurun -- 'bash scripts/r4_headline_quick.sh [ENV=..]'
 out=gpurun_out/r4quick; mkdir -p $out
-env MTG_BENCH_NO_READS=1 MTG_BENCH_NO_E2E=1 "$@" python bench.py --no-children --no-tool --no-ceiling --cpu-sites 0 --cpu-same-sites 0 > $out/bench.json 2> $out/bench.err
+env MTG_BENCH_NO_READS=1 MTG_BENCH_NO_E2E=1 "$@" python bench.py --full --no-children --no-tool --no-ceiling --cpu-sites 0 --cpu-same-sites 0 > $out/bench.json 2> $out/bench.err
 python - $out/bench.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

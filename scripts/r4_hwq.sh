@@ -4,7 +4,7 @@
 out=gpurun_out/r4hwq; mkdir -p $out
 W=$1; shift
 for q in "$@"; do
-    env MTG_BENCH_NO_READS=1 MTG_BENCH_NO_E2E=1 GPU_MAX_HW_QUEUES=$q python bench.py --workload $W --cpu-sites 0 --cpu-same-sites 0 --no-children --no-tool --no-ceiling > $out/$W.$q.json 2> $out/$W.$q.err
+    env MTG_BENCH_NO_READS=1 MTG_BENCH_NO_E2E=1 GPU_MAX_HW_QUEUES=$q python bench.py --full --workload $W --cpu-sites 0 --cpu-same-sites 0 --no-children --no-tool --no-ceiling > $out/$W.$q.json 2> $out/$W.$q.err
     python - $W $q $out/$W.$q.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[3]) if l.startswith("{")][-1])

@@ -5,7 +5,7 @@ out=gpurun_out/r4sec
 mkdir -p $out
 : > $out/summary.txt
 for w in ${WORKLOADS:-human-tips human-het human-indel}; do
-    MTG_BENCH_NO_READS=1 MTG_BENCH_NO_E2E=1 python bench.py --workload $w --cpu-sites 6000 --cpu-index-seqs 12000 --cpu-same-sites 0 --no-children --no-tool --no-ceiling > $out/$w.json 2> $out/$w.err
+    MTG_BENCH_NO_READS=1 MTG_BENCH_NO_E2E=1 python bench.py --full --workload $w --cpu-sites 6000 --cpu-index-seqs 12000 --cpu-same-sites 0 --no-children --no-tool --no-ceiling > $out/$w.json 2> $out/$w.err
     python - $w $out/$w.json >> $out/summary.txt <<'PY'
 import json, sys
 w, p = sys.argv[1], sys.argv[2]

@@ -5,7 +5,7 @@ out=gpurun_out/r4text
 mkdir -p $out
 run() {
     name=$1; shift
-    env MTG_BENCH_NO_READS=1 MTG_BENCH_NO_E2E=1 "$@" python bench.py --no-children --no-tool --no-ceiling --cpu-sites 0 --cpu-same-sites 0 > $out/$name.json 2> $out/$name.err
+    env MTG_BENCH_NO_READS=1 MTG_BENCH_NO_E2E=1 "$@" python bench.py --full --no-children --no-tool --no-ceiling --cpu-sites 0 --cpu-same-sites 0 > $out/$name.json 2> $out/$name.err
     python - $name $out/$name.json <<'PY'
 import json, sys
 try:

@@ -10,7 +10,7 @@ run() { # mode writers-per-file threads inflight
   if [ $2 = default ]; then unset MTG_CLI_WRITERS; else export MTG_CLI_WRITERS=$2; fi
   if [ $3 = default ]; then unset MTG_POOL_THREADS; else export MTG_POOL_THREADS=$3; fi
   if [ $4 = default ]; then unset MTG_CLI_IN_FLIGHT; else export MTG_CLI_IN_FLIGHT=$4; fi
-  MTG_BENCH_NO_E2E=1 MTG_BENCH_NO_READS=1 MTG_TOOL_TIMERS=1 python3 bench.py $B 2> $O/tool.err | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); t=d['tool']; print('format on the $1, writers per file $2, MTG_POOL_THREADS=$3, workers per device $4: tool %.2f M sites/s (%.3f s, %.2f GB/s out, identical %s)  prepared %.1f  text %.1f' % (d['tool_sites_per_s']/1e6, t['seconds'], t['output_GBps'], t['sequences_identical_to_truth'], d['value']/1e6, d['value_from_host_text']/1e6))"
+  MTG_BENCH_NO_E2E=1 MTG_BENCH_NO_READS=1 MTG_TOOL_TIMERS=1 python3 bench.py --full $B 2> $O/tool.err | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); t=d['tool']; print('format on the $1, writers per file $2, MTG_POOL_THREADS=$3, workers per device $4: tool %.2f M sites/s (%.3f s, %.2f GB/s out, identical %s)  prepared %.1f  text %.1f' % (d['tool_sites_per_s']/1e6, t['seconds'], t['output_GBps'], t['sequences_identical_to_truth'], d['value']/1e6, d['value_from_host_text']/1e6))"
   grep "\[tool\]" $O/tool.err | tail -2
 }
 {

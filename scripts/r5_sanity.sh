@@ -3,7 +3,7 @@
 # bubbles / whose gaps are multi-contig under the variants of the tuning table that change who does what: the light walk kernel forced on and off,
 # the host's general path, no lean gaps, several launches per batch (the head region and the work lists across launches), the tool's small batches
 cd $GRAFT_REPO_ROOT
-for args in "--workload tiny --host-strings --cpu-sites 0 --no-ceiling" "--workload ecoli --steps 10 --warmup 2" "--workload tiny --cpu-sites 100"; do echo "== bench.py $args"; MTG_BENCH_NO_READS=1 timeout 500 python bench.py $args 2>/tmp/err.txt | python3 -c "
+for args in "--workload tiny --host-strings --cpu-sites 0 --no-ceiling" "--workload ecoli --steps 10 --warmup 2" "--workload tiny --cpu-sites 100"; do echo "== bench.py $args"; MTG_BENCH_NO_READS=1 timeout 500 python bench.py --full $args 2>/tmp/err.txt | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print({k:d.get(k) for k in ('value','value_from_host_strings','value_from_host_text','tool_sites_per_s','filled_sequences_identical_to_truth')}, (d.get('cpu_baseline') or {}).get('identical_to_hip'))" || tail -5 /tmp/err.txt; done

@@ -6,7 +6,7 @@ T=${1:-r6pmc}; W=${2:-human-indel}; shift; shift
 O=gpurun_out/$T; rm -rf $O; mkdir -p $O
 B="--cpu-sites 0 --no-ceiling --no-secondary --no-children --workload $W --in-flight 1 --steps 6 --warmup 2 --repeats 1 --batches 3"
 for C in ${@:-FETCH_SIZE WRITE_SIZE TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum}; do
-  rocprofv3 --pmc $C --output-format csv -d $O/pmc_$C -o pmc -- python3 bench.py $B --detail $O/detail_$C.json > /dev/null 2> $O/pmc_$C.err
+  rocprofv3 --pmc $C --output-format csv -d $O/pmc_$C -o pmc -- python3 bench.py --full $B --detail $O/detail_$C.json > /dev/null 2> $O/pmc_$C.err
 done
 python3 - "$O" <<'PY'
 import csv, glob, os, sys, json

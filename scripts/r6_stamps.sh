@@ -7,6 +7,6 @@ export MTG_LIBRARY_PATH=$GRAFT_REPO_ROOT/mindthegap_amd/lib_stamps/libmtgfill.so
 : > $O
 for W in ${@:-human-indel human-het human}; do
   echo "== $W" >> $O
-  timeout 600 python3 bench.py --cpu-sites 0 --no-ceiling --workload $W --steps 3 --warmup 1 --repeats 1 --batches 1 --no-secondary --no-children --in-flight 1 --detail gpurun_out/stamps_detail.json 2>&1 | grep -E "stamps" | tail -5 >> $O
+  timeout 600 python3 bench.py --full --cpu-sites 0 --no-ceiling --workload $W --steps 3 --warmup 1 --repeats 1 --batches 1 --no-secondary --no-children --in-flight 1 --detail $(dirname $O)/stamps_detail.json 2>&1 | grep -E "stamps" | tail -5 >> $O
 done
 cat $O
