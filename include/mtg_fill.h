@@ -244,6 +244,29 @@ int mtg_formatted_get(const mtg_formatted* t, mtg_formatted_view* v);
 void mtg_formatted_free(mtg_formatted* t);
 /* and the filled sequences laid out in seq_out as with mtg_fill_batch_serial */
 int mtg_fill_text_serial(const mtg_index* idx, const mtg_params* p, const mtg_text_gaps* g, char* seq_out, uint64_t cap, uint64_t* seq_bytes, mtg_results** out);
+/* ---- Contig mode at assembly scale: ONE dictionary of all targets, resident on the device, instead of a copy per seed.
+ * The reference builds the dictionary of all contig-end k-mers once (src/Filler.cpp:755-829) and hands every seed a copy without the seed's own
+ * entries (:522-533).  mtg_fill_seeds gives the same results as mtg_fill_batch with those per-seed dictionaries, with these rules:
+ *   - the table: entries [0, n) in the caller's iteration order of the dictionary of all targets (key, value.first, value.second);
+ *   - a seed's dictionary: the table without its `excluded` entries, iterating in the order of a fresh std::unordered_map<std::string, ...>
+ *     into which the remaining entries were inserted in table order (what the reference's per-seed copy does);
+ *   - a seed's early-stop pattern R (targetSequence): the keys of its remaining entries, concatenated in table order;
+ *   - keys of any length: a key shorter than k never matches as a target (as with mtg_fill_batch), R is cut at the real key lengths;
+ *   - THE ONE DIFFERENCE: target_index of a result is a TABLE entry number, not a position in the seed's dictionary.
+ * A table lives on the device of the index it was created with; use it only with that index (a tool with replicas makes one per replica).
+ * Keys, names and flags are copied: the caller's arrays may go after mtg_targets_create returns.  Without a device: MTG_ERR_NO_DEVICE. */
+typedef struct mtg_targets mtg_targets;
+int mtg_targets_create(const mtg_index* idx, const char* const* keys, const char* const* names, const uint8_t* is_rc, size_t n, mtg_targets** out);
+void mtg_targets_free(mtg_targets* t);
+/* device memory the table holds (encoded keys, packed key text, the piece indexes made so far) */
+int mtg_targets_device_bytes(const mtg_targets* t, uint64_t* bytes);
+typedef struct mtg_seed {
+    const char* source;          /* sourceSequence */
+    const uint32_t* excluded;    /* ascending entry numbers of the table this seed leaves out (src/Filler.cpp:527); may be NULL when n_excluded == 0 */
+    uint32_t n_excluded;
+    int is_anchor_repeated, reverse;
+} mtg_seed;
+int mtg_fill_seeds(const mtg_index* idx, const mtg_params* p, const mtg_targets* t, const mtg_seed* seeds, size_t n, mtg_results** out);
 const mtg_gap_result* mtg_results_get(const mtg_results* r, size_t i);
 /* Every pointer obtained from r dies here.  The library keeps the storage of up to six freed result sets (a few hundred bytes per
  * gap plus the sequences) and hands it to the next batches, which then pay no allocation, page fault or memset. */

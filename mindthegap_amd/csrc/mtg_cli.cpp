@@ -1110,11 +1110,72 @@ static int run_contig(const Replicas& R, const mtg_params& P, const Options& O, 
         OutText out;
         size_t n = 0, filled = 0, multiple = 0;
     };
-    const size_t B = std::max<size_t>(1, cli_batch_size() / std::max<size_t>(1, all_targets.size() / 8)), nb = (seeds.size() + B - 1) / B; /* a gap carries the whole dictionary: fewer per batch */
+    /* The dictionary of all targets goes to every device ONCE (mtg_fill_seeds): a seed carries only the entries it leaves out.  CONTIG_PER_SEED of
+     * the tuning table: every seed gets its own copy, as until round 6 (mtg_fill_batch) */
+    const bool per_seed = tune::on(tune::T_CONTIG_PER_SEED);
+    struct Tables {
+        std::vector<std::pair<const mtg_index*, mtg_targets*>> t;
+        ~Tables() { for (auto& e : t) mtg_targets_free(e.second); }
+        const mtg_targets* of(const mtg_index* idx) const { for (auto& e : t) if (e.first == idx) return e.second; return nullptr; }
+    } tables;
+    if (!per_seed)
+        for (const mtg_index* ri : R.idx) {
+            mtg_targets* tt = nullptr;
+            if (int rc = mtg_targets_create(ri, T.seq.data(), T.pname.data(), T.rc.data(), T.seq.size(), &tt)) return rc;
+            tables.t.push_back({ri, tt});
+        }
+    const size_t B = per_seed ? std::max<size_t>(1, cli_batch_size() / std::max<size_t>(1, all_targets.size() / 8)) /* a gap carries the whole dictionary: fewer per batch */
+                              : cli_batch_size(),
+                 nb = (seeds.size() + B - 1) / B;
     std::mutex bm;
     std::vector<std::unique_ptr<Batch>> batches(nb);
     const auto next = [&](size_t b) -> bool { return b < nb; };
-    const auto process = [&](size_t b, const mtg_index* idx) -> int {
+    const DictView table_view{T.name.data(), T.rc.data(), nullptr}; /* mtg_fill_seeds: target numbers are table numbers */
+    const auto process_table = [&](size_t b, const mtg_index* idx) -> int {
+        std::unique_ptr<Batch> bt(new Batch());
+        bt->s0 = b * B; bt->s1 = std::min(seeds.size(), (b + 1) * B);
+        const double tp0 = clock_ms();
+        static const std::vector<uint32_t> none;
+        std::vector<mtg_seed> sd(bt->s1 - bt->s0);
+        for (size_t si = bt->s0; si < bt->s1; si++) {
+            const auto own = T.by_seed_name.find(seeds[si].first);
+            const std::vector<uint32_t>& out = own == T.by_seed_name.end() ? none : own->second; /* ascending */
+            mtg_seed& s = sd[si - bt->s0];
+            s.source = seeds[si].second.c_str();
+            s.excluded = out.data();
+            s.n_excluded = (uint32_t)out.size();
+            s.is_anchor_repeated = 0;
+            s.reverse = 0;
+        }
+        const double tp1 = clock_ms();
+        if (int rc = mtg_fill_seeds(idx, &P, tables.of(idx), sd.data(), sd.size(), &bt->run.h)) return rc;
+        const double tp2 = clock_ms();
+        us_prep += (long)((tp1 - tp0) * 1e3); us_run += (long)((tp2 - tp1) * 1e3);
+        for (size_t i = bt->s0; i < bt->s1; i++) {
+            const size_t j = i - bt->s0;
+            const std::string& seedName = seeds[i].first;
+            const bool isRc = seedName.length() >= 3 && seedName.compare(seedName.length() - 3, 3, "_Rc") == 0;
+            std::vector<mtg_filled> kept;
+            for (auto& s : sols_of(bt->run[j])) { /* drop loops: target == seed reversed, :540-557 */
+                const std::string& tn = T.name[(size_t)s.target_index];
+                const std::string revTargetName = T.rc[(size_t)s.target_index] ? tn : tn + "_Rc";
+                if (revTargetName != seedName) kept.push_back(s);
+            }
+            Sols ks;
+            ks.p = kept.data(); ks.n = kept.size();
+            write_filled(bt->out, false, table_view, ks, seedName, info_string(bt->run[j]));
+            write_gfa(bt->out, trim, table_view, ks, seedName, isRc);
+            if (kept.empty() && O.extend) write_extension(bt->out, bt->run[j].extension, seedName, "", seeds[i].second);
+            bt->n++;
+            bt->filled += kept.size() > 0;
+            bt->multiple += kept.size() > 1;
+        }
+        us_text += (long)((clock_ms() - tp2) * 1e3);
+        std::lock_guard<std::mutex> lk(bm);
+        batches[b] = std::move(bt);
+        return MTG_OK;
+    };
+    const auto process_per_seed = [&](size_t b, const mtg_index* idx) -> int {
         std::unique_ptr<Batch> bt(new Batch());
         bt->s0 = b * B; bt->s1 = std::min(seeds.size(), (b + 1) * B);
         bt->gaps.resize(bt->s1 - bt->s0);
@@ -1183,7 +1244,7 @@ static int run_contig(const Replicas& R, const mtg_params& P, const Options& O, 
         S.nb_filled += (int)bt->filled;
         S.nb_multiple += (int)bt->multiple;
     };
-    const int rc_all = run_batches(R, next, process, consume);
+    const int rc_all = per_seed ? run_batches(R, next, process_per_seed, consume) : run_batches(R, next, process_table, consume);
     if (dbg) fprintf(stderr, "  [contig] %zu seeds x %zu targets in %zu batches: contigs read + dictionary %.1f ms, batches %.1f ms wall (workers' time: dictionaries of the seeds %.1f, mtg_fill_batch %.1f, text %.1f ms)\n",
                      seeds.size(), all_targets.size(), nb, t_setup - t_begin, clock_ms() - t_setup, us_prep / 1e3, us_run / 1e3, us_text / 1e3);
     return rc_all;

@@ -127,10 +127,7 @@ __device__ __forceinline__ void stage_a_lane(uint8_t* zero, uint8_t* raw, uint8_
     const uint32_t g = ids ? ids[slot] : slot; /* gap id in the input arrays; scratch is indexed by slot */
     GapScratch S = carve(cfg, zero, raw, ilv, head, slot);
     S.snp_fast = 1; /* the walking lane answers the strict SNP pattern itself */
-    SwfPattern R;
-    R.words = rwords + roff[g];
-    R.rlen = rlen[g];
-    R.r0 = r0[g];
+    const SwfPattern R = swf_pattern(rwords, roff, rlen, r0, g);
     GapOut o;
 #ifdef MTG_BUBBLE_TIMING
     const uint64_t t0 = wall_clock64();
@@ -215,10 +212,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MTG_FIN
     const uint32_t g = ids ? ids[slot] : slot;
     GapScratch S = carve(cfg, zero, raw, ilv, head, slot);
     S.snp_fast = 1;
-    SwfPattern R;
-    R.words = rwords + roff[g];
-    R.rlen = rlen[g];
-    R.r0 = r0[g];
+    const SwfPattern R = swf_pattern(rwords, roff, rlen, r0, g);
     GapOut o;
     const uint64_t target = lean_target(li, g, ix.k);
     stage_a_walk<WALK_FINISH, G>(ix, cfg, S, 0, R, o, &lds[lane / G]);
@@ -240,10 +234,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MTG_STA
     const uint32_t g = ids ? ids[slot] : slot;
     GapScratch S = carve(cfg, zero, raw, ilv, head, slot);
     S.snp_fast = 1;
-    SwfPattern R;
-    R.words = rwords + roff[g];
-    R.rlen = rlen[g];
-    R.r0 = r0[g];
+    const SwfPattern R = swf_pattern(rwords, roff, rlen, r0, g);
     GapOut o;
     const uint64_t target = lean_target(li, g, ix.k);
     stage_a_walk<WALK_FINISH, 1>(ix, cfg, S, 0, R, o, nullptr);
@@ -301,6 +292,13 @@ __global__ void k_encode_targets(const uint8_t* __restrict__ traw, uint64_t* __r
     tbad[t] = bad;
 }
 
+/* the piece index of a shared target table (mtg_fill_seeds): every entry's pieces under gid 0, a thread per entry */
+__global__ void __launch_bounds__(256) k_table_index(uint32_t* head, uint32_t* next, uint32_t mask, const uint64_t* __restrict__ tle, const uint64_t* __restrict__ tbad, uint32_t n, uint32_t nb_mis, int k)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n) post_index_add(head, next, mask, 0u, t, tle[t], tbad[t], nb_mis, k);
+}
+
 /* terminal-node search + coverage of the single-contig solution, one wave per gap; leaves the slot's record with what the gap will
  * contribute to the arrays of its batch (mtg_emit.h: emit_plan).  Where it goes is decided by the scan kernels below. */
 /* the piece index of a batch's dictionaries (mtg_post.h): a workgroup per gap and turn, its targets dealt to the threads */
@@ -319,7 +317,8 @@ __global__ void __launch_bounds__(256) k_post_index(uint32_t* head, uint32_t* ne
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MTG_POST_WAVES))) k_post(Index ix, FillCfg cfg, uint8_t* raw, uint8_t* head, const GapOut* __restrict__ outs, const uint32_t* __restrict__ ids,
                                              const uint64_t* __restrict__ tle, const uint64_t* __restrict__ tbad, const uint32_t* __restrict__ toff,
                                              const uint32_t* __restrict__ tcnt, const uint8_t* __restrict__ nbmis, const uint8_t* __restrict__ fast_ok,
-                                             uint32_t want_all, SlotRec* recs, uint32_t n, ParkCtl* park, const uint32_t* __restrict__ pi_head, const uint32_t* __restrict__ pi_next, uint32_t pi_mask)
+                                             uint32_t want_all, SlotRec* recs, uint32_t n, ParkCtl* park, const uint32_t* __restrict__ pi_head, const uint32_t* __restrict__ pi_next, uint32_t pi_mask,
+                                             const uint64_t* __restrict__ rwords, const uint32_t* __restrict__ roff, uint8_t* tie)
 {
     __shared__ uint32_t hist[256];
     __shared__ uint64_t tile[POST_TILE + 2];
@@ -352,10 +351,17 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MTG_POS
             T.nb_mis = nbmis[g];
             T.fast_ok = fast_ok[g];
             T.pi_head = pi_head; T.pi_next = pi_next; T.pi_mask = pi_mask; T.gbase = toff[g]; T.gid = g;
+            uint8_t* tie_g = nullptr;
+            if (tie) { /* a seed of a shared table: the table's piece index (gid 0), its exclusions from the pattern descriptor */
+                const uint64_t* d = rwords + (roff[g] & ~SEED_PATTERN); /* (mtg_traverse.h: swf_pattern) */
+                T.gid = 0;
+                T.excl = d + 2; T.n_excl = (uint32_t)d[1];
+                tie_g = tie + g;
+            }
 #ifdef MTG_POST_DBG /* timing experiments only (scripts/exp_post_parts.sh): parts of the kernel switched off, results wrong */
-            post_gap(ix, cfg, S, o, T, hist, tile, s_blk, po, MTG_POST_DBG);
+            post_gap(ix, cfg, S, o, T, hist, tile, s_blk, po, MTG_POST_DBG, tie_g);
 #else
-            post_gap(ix, cfg, S, o, T, hist, tile, s_blk, po);
+            post_gap(ix, cfg, S, o, T, hist, tile, s_blk, po, 0, tie_g);
 #endif
         }
         /* the record leaves lane 0 in ten 16-byte stores (SlotRec is 16-byte aligned): field by field it made the kernel write 1.1 KB of
@@ -674,6 +680,54 @@ int batch_upload(const mtg_index* idx, FillInput& in)
     in.dev_tenc = t.release();
     return MTG_OK;
 }
+/* ---- the device side of a shared target table (mtg_internal.h: SharedTableOps), made once per table on the null stream */
+namespace {
+int table_upload(const mtg_index* idx, const uint8_t* slots, size_t n, const uint64_t* text, size_t text_words, void** enc, void** d_text)
+{
+    if (int rc = use_device_of(idx)) return rc;
+    DevBuf raw, e, t;
+    HIP_TRY(raw.alloc(n * TARGET_SLOT + 64));
+    HIP_TRY(e.alloc(n * 16 + 64));
+    HIP_TRY(t.alloc(text_words * 8 + 64));
+    if (n) HIP_TRY(hipMemcpy(raw.p, slots, n * TARGET_SLOT, hipMemcpyHostToDevice));
+    if (text_words) HIP_TRY(hipMemcpy(t.p, text, text_words * 8, hipMemcpyHostToDevice));
+    if (n) {
+        hipLaunchKernelGGL(k_encode_targets, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, raw.as<uint8_t>(), e.as<uint64_t>(), e.as<uint64_t>() + n, (uint64_t)n, idx->dev.k);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    *enc = e.release();
+    *d_text = t.release();
+    return MTG_OK;
+}
+int table_piece_index(const mtg_index* idx, const void* enc, size_t n, int nb_mis, void** pi, uint32_t* mask)
+{
+    if (int rc = use_device_of(idx)) return rc;
+    uint64_t cap = 1024;
+    while (cap < 4 * (uint64_t)n) cap <<= 1;
+    DevBuf b;
+    HIP_TRY(b.alloc((cap + 4 * (uint64_t)n) * 4));
+    HIP_TRY(hipMemset(b.p, 0xFF, cap * 4));
+    const uint64_t* le = (const uint64_t*)enc;
+    if (n) {
+        hipLaunchKernelGGL(k_table_index, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, b.as<uint32_t>(), b.as<uint32_t>() + cap, (uint32_t)(cap - 1), le, le + n, (uint32_t)n, (uint32_t)nb_mis, idx->dev.k);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    *mask = (uint32_t)(cap - 1);
+    *pi = b.release();
+    return MTG_OK;
+}
+void table_release(int device, void* p)
+{
+    if (!p) return;
+    (void)hipSetDevice(device);
+    (void)hipFree(p);
+}
+SharedTableOps g_table_ops{table_upload, table_piece_index, table_release};
+struct TableOpsInit { TableOpsInit() { g_shared_ops = &g_table_ops; } } g_table_ops_init;
+} // namespace
+
 void batch_release_device(FillInput& in)
 {
     if (in.dev_a) (void)hipFree(in.dev_a);
@@ -734,11 +788,12 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
     int ws_next = 0;
     auto wsbuf = [&]() { WsBuf b; b.ws = &ws; b.slot = ws_next++; return b; };
     WsBuf d_ina = wsbuf(), d_inb = wsbuf(), d_inc = wsbuf(), d_tenc = wsbuf(), d_ilv = wsbuf(), d_zero = wsbuf(), d_raw = wsbuf(), d_out = wsbuf(), d_rec = wsbuf(), d_ids = wsbuf(), d_dw = wsbuf(),
-          d_dm = wsbuf(), d_combo = wsbuf(), d_blocks = wsbuf(), d_seq = wsbuf(), d_ext = wsbuf(), d_res = wsbuf(), d_fil = wsbuf(), d_tot = wsbuf(), d_rlist = wsbuf(), d_glist = wsbuf(), d_paths = wsbuf(), d_park = wsbuf(), d_ggaps = wsbuf(), d_gsols = wsbuf(), d_gascii = wsbuf(), d_gtmp = wsbuf(), d_gbnd = wsbuf(), d_head = wsbuf(), d_pidx = wsbuf();
+          d_dm = wsbuf(), d_combo = wsbuf(), d_blocks = wsbuf(), d_seq = wsbuf(), d_ext = wsbuf(), d_res = wsbuf(), d_fil = wsbuf(), d_tot = wsbuf(), d_rlist = wsbuf(), d_glist = wsbuf(), d_paths = wsbuf(), d_park = wsbuf(), d_ggaps = wsbuf(), d_gsols = wsbuf(), d_gascii = wsbuf(), d_gtmp = wsbuf(), d_gbnd = wsbuf(), d_head = wsbuf(), d_pidx = wsbuf(), d_tie = wsbuf();
     /* the marshalled input: three blocks, three copies; the targets (block C, text) become k-mers and masks on the device.  A batch that
      * was prepared ahead (mtg_batch) is resident already */
     double t0 = now_ms();
-    const uint64_t n_targets = in.text_mode ? in.n_text_targets : in.traw.size() / TARGET_SLOT;
+    const bool seeds = in.shared.enc != nullptr; /* mtg_fill_seeds: the dictionary is the shared table, resident */
+    const uint64_t n_targets = seeds ? in.shared.n : in.text_mode ? in.n_text_targets : in.traw.size() / TARGET_SLOT;
     /* the events of a batch belong to its workspace: made once (round 4 created and destroyed nine per batch: eighteen runtime calls of the ~50 a
      * batch made, and the runtime serialises them across the caller threads) */
     struct WsEvents {
@@ -795,6 +850,16 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
         da = (const uint8_t*)in.dev_a;
         d_rw = (const uint64_t*)in.dev_b;
         d_tle = (uint64_t*)in.dev_tenc;
+    } else if (seeds) {
+        /* the sources and the pattern descriptors (with the exclusions) go up; the keys are the table's */
+        HIP_TRY(d_ina.alloc(in.bytes_a));
+        HIP_TRY(d_inb.alloc(in.bytes_b));
+        HIP_TRY(hipMemcpyAsync(d_ina.p, in.block_a, in.bytes_a, hipMemcpyHostToDevice, up));
+        HIP_TRY(hipMemcpyAsync(d_inb.p, in.block_b, in.bytes_b, hipMemcpyHostToDevice, up));
+        if (int rc = uploaded()) return rc;
+        da = d_ina.as<uint8_t>();
+        d_rw = d_inb.as<uint64_t>();
+        d_tle = const_cast<uint64_t*>(in.shared.enc);
     } else {
         HIP_TRY(d_ina.alloc(in.bytes_a));
         HIP_TRY(d_inb.alloc(in.bytes_b));
@@ -824,7 +889,15 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
     uint32_t* d_pi_head = nullptr;
     uint32_t* d_pi_next = nullptr;
     uint32_t pi_mask = 0;
-    if (n_targets >= (uint64_t)POST_INDEX_MIN * n && n_targets < (1ull << 30) && !tune::on(tune::T_NO_POST_INDEX)) {
+    uint8_t* d_tie_p = nullptr;
+    if (seeds) { /* the table's own index (gid 0), made once; a byte per gap for the ties the seeds' own dictionary orders decide */
+        d_pi_head = const_cast<uint32_t*>(in.shared.pi);
+        d_pi_next = d_pi_head + (size_t)in.shared.pi_mask + 1;
+        pi_mask = in.shared.pi_mask;
+        HIP_TRY(d_tie.alloc(n));
+        d_tie_p = d_tie.as<uint8_t>();
+        HIP_TRY(hipMemsetAsync(d_tie_p, 0, n, stream));
+    } else if (n_targets >= (uint64_t)POST_INDEX_MIN * n && n_targets < (1ull << 30) && !tune::on(tune::T_NO_POST_INDEX)) {
         uint64_t cap = 1024;
         while (cap < 4 * n_targets) cap <<= 1;
         HIP_TRY(d_pidx.alloc((cap + 4 * n_targets) * 4));
@@ -1059,7 +1132,7 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
              * the others.  Both on the batch's one stream: the general form next to the lean one on a second stream, and the finishing kernel there as
              * well, were built and measured in round 4 (9 and 25 us shorter for one batch alone, no faster with six in flight) and removed in round 5. */
             hipLaunchKernelGGL(k_post, dim3(general_hint), dim3(64), 0, stream, idx->dev, cfg, d_raw.as<uint8_t>(), d_head.as<uint8_t>(), d_out.as<GapOut>(), ids, d_tle, d_tbad, d_toff, d_tcnt, d_mis, d_fok,
-                               in.want_all_contigs ? 1u : 0u, d_rec.as<SlotRec>(), m, park, (const uint32_t*)d_pi_head, (const uint32_t*)d_pi_next, pi_mask);
+                               in.want_all_contigs ? 1u : 0u, d_rec.as<SlotRec>(), m, park, (const uint32_t*)d_pi_head, (const uint32_t*)d_pi_next, pi_mask, d_rw, d_roff, d_tie_p);
             hipLaunchKernelGGL(k_post_lean, dim3((m + 64 / POST_LEAN_G - 1) / (64 / POST_LEAN_G)), dim3(64), 0, stream, idx->dev, cfg, d_raw.as<uint8_t>(), d_head.as<uint8_t>(), d_out.as<GapOut>(), in.want_all_contigs ? 1u : 0u, d_rec.as<SlotRec>(), m);
             /* the dense arrays hold one launch at a time; the two arenas the whole batch */
             const ScanBegin sbegin{{0, 0, arena_used[0], arena_used[1]}};
@@ -1381,6 +1454,11 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
     if (rc == MTG_OK && n_todo) {
         set_error("%zu gap(s) exceeded the largest traversal scratch tier", n_todo);
         rc = MTG_ERR_OVERFLOW;
+    }
+    if (rc == MTG_OK && seeds && in.tie_out) {
+        const hipError_t e = hipMemcpyAsync(in.tie_out, d_tie_p, n, hipMemcpyDeviceToHost, stream);
+        const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(stream) : e;
+        if (e2 != hipSuccess) { set_error("HIP error %s (the seeds' tie flags)", hipGetErrorString(e2)); rc = MTG_ERR_NO_DEVICE; }
     }
     if (launches > 1) sink.in_gap_order = false;
     sink.device_records_whole = rc == MTG_OK && launches == 1 && st.n_retried_gaps == 0 && special.special.empty();

@@ -13,6 +13,7 @@
  * The temp-file round trips of the reference (contigs FASTA + dot graph per gap) are not reproduced.
  */
 #include "mtg_internal.h"
+#include "mtg_dict_order.h"
 #include <unistd.h>
 
 #include <algorithm>
@@ -70,6 +71,8 @@ int mtg_tuning_set(const char* name, const char* value)
 using namespace mtg;
 
 namespace mtgi {
+
+SharedTableOps* g_shared_ops = nullptr; /* set by the HIP translation unit */
 
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -1148,7 +1151,8 @@ struct FormatReq {
     mtg_formatted* out;
 };
 int fill_marshalled(const mtg_index* idx, const mtg_params* p, const mtgi::FillInput& in, const mtg_gap* gaps, size_t n, char* seq_out, uint64_t seq_cap, uint64_t* seq_bytes,
-                    mtg_results** out, double t_begin, char* d_seq_out = nullptr, const WireReq* wire = nullptr, const mtg_text_gaps* tg = nullptr, const FormatReq* fmt = nullptr)
+                    mtg_results** out, double t_begin, char* d_seq_out = nullptr, const WireReq* wire = nullptr, const mtg_text_gaps* tg = nullptr, const FormatReq* fmt = nullptr,
+                    const mtgi::TargetSpan* table = nullptr)
 {
     using namespace mtgi;
     const bool dbg = tune::on(tune::T_DEBUG_TIMERS);
@@ -1231,6 +1235,7 @@ int fill_marshalled(const mtg_index* idx, const mtg_params* p, const mtgi::FillI
             w.source = std::string_view(a.source, strlen(a.source));
             w.anchor_repeated = a.is_anchor_repeated != 0;
             w.reverse = a.reverse != 0;
+            if (table) { w.targets = *table; return; } /* mtg_fill_seeds: the target numbers are the shared table's */
             w.target_store.resize((size_t)std::max(a.n_targets, 0));
             for (int t = 0; t < a.n_targets; t++) {
                 Target& T = w.target_store[(size_t)t];
@@ -1245,7 +1250,7 @@ int fill_marshalled(const mtg_index* idx, const mtg_params* p, const mtgi::FillI
         if (rc == MTG_INTERNAL_RETRY_HOST_GENERAL) {
             /* once more, every multi-contig gap by the host's path (its contigs come along): this attempt's result object goes back to the pool */
             struct Flag { Flag() { tl_host_general = true; } ~Flag() { tl_host_general = false; } } flag;
-            return fill_marshalled(idx, p, in, gaps, n, seq_out, seq_cap, seq_bytes, out, t_begin, d_seq_out, wire, tg, fmt);
+            return fill_marshalled(idx, p, in, gaps, n, seq_out, seq_cap, seq_bytes, out, t_begin, d_seq_out, wire, tg, fmt, table);
         }
         if (rc) return rc;
         size_t total = 0;
@@ -1836,4 +1841,324 @@ int mtg_stage_a_batch(const mtg_index* idx, const mtg_params* p, const char* con
 size_t mtg_contigs_count(const mtg_contigs* c, size_t gap) { return (c && gap < c->c.size()) ? c->c[gap].size() : 0; }
 const char* mtg_contigs_get(const mtg_contigs* c, size_t gap, size_t i) { return (c && gap < c->c.size() && i < c->c[gap].size()) ? c->c[gap][i].c_str() : nullptr; }
 void mtg_contigs_free(mtg_contigs* c) { delete c; }
+}
+
+/* ------------------------------------------------------------------------------------------------ contig mode: the shared target table */
+/* The dictionary of all targets (include/mtg_fill.h: mtg_targets_create), kept on the host for the paths that need strings (the multi-contig gaps'
+ * names, the per-seed path) and on the device for the terminal search (encoded keys, piece index) and the early stop (packed key text). */
+struct mtg_targets {
+    int device = 0, k = 0;
+    size_t n = 0;
+    std::vector<std::string> key, name;
+    std::vector<uint8_t> rc;
+    std::vector<mtgi::Target> view;  /* the multi-contig path's dictionary: entry numbers are table numbers */
+    std::vector<uint64_t> key_off;   /* n + 1: first nucleotide of every key in the key text */
+    std::vector<uint8_t> plain;      /* the key is upper-case ACGT only (an early-stop pattern with any other character never matches) */
+    size_t n_unplain = 0;
+    std::vector<size_t> code;        /* std::hash of every key: the order of a seed's own dictionary (mtg_dict_order.h) */
+    void* enc = nullptr;             /* device: le[n] | bad[n] */
+    void* text = nullptr;            /* device: the keys one after the other, 2-bit packed */
+    uint64_t text_words = 0;
+    std::mutex m;
+    std::vector<std::pair<int, std::pair<void*, uint32_t>>> pidx; /* nb_mis -> piece index, mask */
+    ~mtg_targets()
+    {
+        if (!mtgi::g_shared_ops) return;
+        mtgi::g_shared_ops->release(device, enc);
+        mtgi::g_shared_ops->release(device, text);
+        for (auto& e : pidx) mtgi::g_shared_ops->release(device, e.second.first);
+    }
+};
+
+namespace {
+using namespace mtgi;
+/* the seeds of one shared-table batch: block A as marshal_gaps writes it (toff 0, tcnt = the table), block B the pattern descriptors */
+int run_seed_batch(const mtg_index* idx, const mtg_params* p, const mtg_targets* t, const mtg_seed* seeds, const std::vector<uint32_t>& which, const uint32_t* pi, uint32_t pi_mask,
+                   std::vector<uint8_t>& tie, mtg_results** out)
+{
+    const size_t n = which.size();
+    const int k = t->k;
+    const double t_begin = now_ms();
+    WorkspaceLock batch_lock = acquire_workspace(idx);
+    FillInput in;
+    in.k = k;
+    in.ws = batch_lock.ws;
+    in.resize(n);
+    uint64_t rw = 0;
+    for (size_t i = 0; i < n; i++) { in.roff[i] = (uint32_t)rw; rw += 2 + 3 * (uint64_t)seeds[which[i]].n_excluded; }
+    if (rw >> 31) { set_error("batch too large"); return MTG_ERR_ARG; }
+    in.alloc_b(rw, 0);
+    in.shared.enc = (const uint64_t*)t->enc;
+    in.shared.n = (uint32_t)t->n;
+    in.shared.pi = pi;
+    in.shared.pi_mask = pi_mask;
+    tie.assign(n, 0);
+    in.tie_out = tie.data();
+    std::vector<mtg_gap> gaps(n); /* what the multi-contig path reads of a gap: its source and flags (the dictionary is the table) */
+    parallel_for(n, p->nb_host_threads, [&](size_t i) {
+        const mtg_seed& s = seeds[which[i]];
+        const uint8_t fl = (uint8_t)((s.is_anchor_repeated ? mtg::GAPF_REPEATED : 0) | (s.reverse ? mtg::GAPF_REVERSE : 0));
+        const uint32_t w0 = in.roff[i];
+        in.set_common(i, std::string_view(s.source), std::string_view(), s.is_anchor_repeated ? 0 : p->nb_mis_allowed, fl); /* src/Filler.cpp:859-863 */
+        /* R: the keys of the entries the seed keeps, in table order -- the table's key text with the excluded keys cut out */
+        uint64_t* d = in.rwords.p + w0;
+        d[0] = (uint64_t)(uintptr_t)t->text;
+        d[1] = s.n_excluded;
+        uint64_t len = t->key_off[t->n];
+        size_t unplain = t->n_unplain;
+        for (uint32_t j = 0; j < s.n_excluded; j++) {
+            const uint32_t e = s.excluded[j];
+            d[2 + 3 * j] = t->key_off[e];
+            d[3 + 3 * j] = t->key_off[e + 1] - t->key_off[e];
+            d[4 + 3 * j] = e;
+            len -= t->key_off[e + 1] - t->key_off[e];
+            unplain -= t->plain[e] ? 0 : 1;
+        }
+        in.roff[i] = w0 | SEED_PATTERN;
+        in.toff[i] = 0;
+        in.tcnt[i] = (uint32_t)t->n;
+        if (unplain) { in.rlen[i] = 0xFFFFFFFFu; in.r0[i] = 0; }
+        else {
+            in.rlen[i] = (uint32_t)len;
+            uint64_t r0 = 0;
+            if (len >= (uint64_t)k) { /* its first k-mer (first nucleotide in the highest field) */
+                int got = 0;
+                uint32_t x = 0;
+                for (uint32_t e = 0; e < t->n && got < k; e++) {
+                    if (x < s.n_excluded && s.excluded[x] == e) { x++; continue; }
+                    for (size_t c = 0; c < t->key[e].size() && got < k; c++, got++) r0 = (r0 << 2) | nt_code((unsigned char)t->key[e][c]);
+                }
+            }
+            in.r0[i] = r0;
+        }
+        gaps[i].source = s.source;
+        gaps[i].target = "";
+        gaps[i].is_anchor_repeated = s.is_anchor_repeated;
+        gaps[i].reverse = s.reverse;
+    }, 64);
+    const TargetSpan table{t->view.data(), (uint32_t)t->n};
+    return fill_marshalled(idx, p, in, gaps.data(), n, nullptr, 0, nullptr, out, t_begin, nullptr, nullptr, nullptr, nullptr, &table);
+}
+
+/* the seeds in `which` by the per-seed path: each gets its own dictionary (the table without its entries, in the order of a fresh unordered_map) and
+ * pattern, as the reference builds them (src/Filler.cpp:522-533), and goes through mtg_fill_batch.  parts receives the result sets and, per seed, the
+ * table entry of every position of its dictionary. */
+struct PerSeedPart {
+    mtg_results* r = nullptr;
+    std::vector<std::vector<uint32_t>> order;
+};
+int run_per_seed(const mtg_index* idx, const mtg_params* p, const mtg_targets* t, const mtg_seed* seeds, const std::vector<uint32_t>& which, std::vector<PerSeedPart>& parts)
+{
+    const size_t PAIRS = (size_t)1 << 24; /* (seed, target) pairs per call */
+    size_t a = 0;
+    while (a < which.size()) {
+        size_t b = a, pairs = 0;
+        while (b < which.size() && (b == a || pairs + t->n <= PAIRS)) { pairs += t->n; b++; }
+        PerSeedPart part;
+        part.order.resize(b - a);
+        std::vector<std::string> pattern(b - a);
+        std::vector<std::vector<const char*>> ks(b - a), ns(b - a);
+        std::vector<std::vector<uint8_t>> rcs(b - a);
+        std::vector<mtg_gap> gaps(b - a);
+        parallel_for(b - a, p->nb_host_threads, [&](size_t j) {
+            static thread_local mtgcli::DictOrder dict_order;
+            const mtg_seed& s = seeds[which[a + j]];
+            std::vector<uint8_t> skip(t->n, 0);
+            for (uint32_t x = 0; x < s.n_excluded; x++) skip[s.excluded[x]] = 1;
+            for (uint32_t e = 0; e < t->n; e++) if (!skip[e]) pattern[j] += t->key[e];
+            dict_order.order(t->code.data(), (uint32_t)t->n, skip.data(), part.order[j]);
+            for (uint32_t e : part.order[j]) { ks[j].push_back(t->key[e].c_str()); ns[j].push_back(t->name[e].c_str()); rcs[j].push_back(t->rc[e]); }
+            mtg_gap& g = gaps[j];
+            g.source = s.source;
+            g.target = pattern[j].c_str();
+            g.n_targets = (int)ks[j].size();
+            g.target_seqs = ks[j].data();
+            g.target_names = ns[j].data();
+            g.target_is_rc = rcs[j].data();
+            g.is_anchor_repeated = s.is_anchor_repeated;
+            g.reverse = s.reverse;
+        }, 1);
+        if (int rc = mtg_fill_batch(idx, p, gaps.data(), gaps.size(), &part.r)) return rc;
+        parts.push_back(std::move(part));
+        a = b;
+    }
+    return MTG_OK;
+}
+} // namespace
+
+extern "C" {
+int mtg_targets_create(const mtg_index* idx, const char* const* keys, const char* const* names, const uint8_t* is_rc, size_t n, mtg_targets** out)
+{
+    using namespace mtgi;
+    if (!idx || !out || (n && (!keys || !names))) { set_error("null argument"); return MTG_ERR_ARG; }
+    if (n >> 30) { set_error("a table of more than 2^30 targets"); return MTG_ERR_ARG; }
+    for (size_t i = 0; i < n; i++) if (!keys[i] || !names[i]) { set_error("entry %zu: null field", i); return MTG_ERR_ARG; }
+    std::unique_ptr<mtg_targets> t(new mtg_targets());
+    t->device = idx->device;
+    t->k = idx->dev.k;
+    t->n = n;
+    t->key.resize(n); t->name.resize(n); t->rc.resize(n); t->code.resize(n); t->plain.resize(n); t->key_off.resize(n + 1);
+    uint64_t off = 0;
+    for (size_t i = 0; i < n; i++) {
+        t->key[i] = keys[i];
+        t->name[i] = names[i];
+        t->rc[i] = is_rc && is_rc[i] ? 1 : 0;
+        t->code[i] = std::hash<std::string>()(t->key[i]);
+        t->key_off[i] = off;
+        off += t->key[i].size();
+        t->plain[i] = all_upper_acgt(t->key[i].data(), t->key[i].size()) ? 1 : 0;
+        t->n_unplain += t->plain[i] ? 0 : 1;
+    }
+    t->key_off[n] = off;
+    if (off >= 0xFFFFFFFFull) { set_error("the keys of the table hold %llu nucleotides (at most 2^32 - 2)", (unsigned long long)off); return MTG_ERR_ARG; }
+    t->view.resize(n);
+    for (size_t i = 0; i < n; i++) { t->view[i].seq = t->key[i]; t->view[i].name = t->name[i]; t->view[i].is_rc = t->rc[i] != 0; }
+    if (g_shared_ops) {
+        /* the keys' first k characters in TARGET_SLOT slots (encode_target on the device) and the key text packed */
+        std::vector<uint8_t> slots(n * TARGET_SLOT + 64, 0);
+        for (size_t i = 0; i < n; i++) {
+            uint8_t* sl = slots.data() + i * TARGET_SLOT;
+            const bool usable = t->key[i].size() >= (size_t)t->k;
+            if (usable) memcpy(sl, t->key[i].data(), (size_t)t->k);
+            sl[TARGET_SLOT - 1] = usable ? 1 : 0;
+        }
+        t->text_words = off / 32 + 1;
+        std::vector<uint64_t> text(t->text_words, 0);
+        for (size_t i = 0; i < n; i++)
+            for (size_t c = 0; c < t->key[i].size(); c++) {
+                const uint64_t j = t->key_off[i] + c;
+                text[j >> 5] |= (uint64_t)nt_code((unsigned char)t->key[i][c]) << (2 * (j & 31));
+            }
+        if (int rc = g_shared_ops->upload(idx, slots.data(), n, text.data(), text.size(), &t->enc, &t->text)) return rc;
+    }
+    *out = t.release();
+    return MTG_OK;
+}
+void mtg_targets_free(mtg_targets* t) { delete t; }
+int mtg_targets_device_bytes(const mtg_targets* t, uint64_t* bytes)
+{
+    if (!t || !bytes) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    if (!t->enc) { *bytes = 0; return MTG_OK; }
+    uint64_t b = 16 * (uint64_t)t->n + 64 + 8 * t->text_words + 64;
+    std::lock_guard<std::mutex> lk(const_cast<mtg_targets*>(t)->m);
+    for (auto& e : t->pidx) b += 4 * ((uint64_t)e.second.second + 1 + 4 * (uint64_t)t->n);
+    *bytes = b;
+    return MTG_OK;
+}
+
+int mtg_fill_seeds(const mtg_index* idx, const mtg_params* p, const mtg_targets* t, const mtg_seed* seeds, size_t n, mtg_results** out)
+{
+    using namespace mtgi;
+    if (!idx || !p || !t || !out || (n && !seeds)) { set_error("null argument"); return MTG_ERR_ARG; }
+    if (t->device != idx->device || t->k != idx->dev.k) { set_error("the table belongs to another device or k"); return MTG_ERR_ARG; }
+    for (size_t i = 0; i < n; i++) {
+        const mtg_seed& s = seeds[i];
+        if (!s.source || (s.n_excluded && !s.excluded)) { set_error("seed %zu: null field", i); return MTG_ERR_ARG; }
+        if ((int)strlen(s.source) < t->k) { set_error("gap %zu: source sequence shorter than k", i); return MTG_ERR_ARG; }
+        for (uint32_t j = 0; j < s.n_excluded; j++)
+            if (s.excluded[j] >= t->n || (j && s.excluded[j] <= s.excluded[j - 1])) { set_error("seed %zu: the excluded entries are not ascending table numbers", i); return MTG_ERR_ARG; }
+    }
+    /* the shared table serves the seeds whose terminal search goes through its piece index (mtg_post.h: a dictionary of POST_INDEX_MIN entries or
+     * more, pieces of 8 nucleotides or more, the batch's mismatch allowance); the others -- and the seeds the device flags because the order of their
+     * own dictionary decides a tie -- take the per-seed path */
+    const int nbm = p->nb_mis_allowed;
+    const bool table_ok = g_shared_ops && t->enc && t->n >= (size_t)POST_INDEX_MIN && nbm >= 0 && post_index_usable(t->k, (uint32_t)nbm) && !tune::on(tune::T_CONTIG_PER_SEED) &&
+                          !tune::on(tune::T_NO_POST_INDEX);
+    std::vector<uint32_t> shared, per_seed;
+    for (size_t i = 0; i < n; i++) {
+        const mtg_seed& s = seeds[i];
+        const bool ok = table_ok && (s.is_anchor_repeated ? 0 : nbm) == nbm && t->n - s.n_excluded >= (size_t)POST_INDEX_MIN;
+        (ok ? shared : per_seed).push_back((uint32_t)i);
+    }
+    mtg_results* rs = nullptr;
+    struct Free { mtg_results*& r; ~Free() { if (r) mtg_results_free(r); } } free_rs{rs};
+    std::vector<uint8_t> tie;
+    if (!shared.empty()) {
+        const uint32_t* pi = nullptr;
+        uint32_t mask = 0;
+        {
+            mtg_targets* tm = const_cast<mtg_targets*>(t);
+            std::lock_guard<std::mutex> lk(tm->m);
+            for (auto& e : tm->pidx) if (e.first == nbm) { pi = (const uint32_t*)e.second.first; mask = e.second.second; }
+            if (!pi) {
+                void* b = nullptr;
+                if (int rc = g_shared_ops->piece_index(idx, tm->enc, tm->n, nbm, &b, &mask)) return rc;
+                tm->pidx.push_back({nbm, {b, mask}});
+                pi = (const uint32_t*)b;
+            }
+        }
+        if (int rc = run_seed_batch(idx, p, t, seeds, shared, pi, mask, tie, &rs)) return rc;
+        for (size_t i = 0; i < shared.size(); i++) if (tie[i]) per_seed.push_back(shared[i]);
+    }
+    if (tune::on(tune::T_DEBUG_TIMERS)) {
+        size_t nt = 0;
+        for (uint8_t x : tie) nt += x != 0;
+        fprintf(stderr, "  [fill_seeds] %zu seeds: %zu from the shared table, %zu of them with a tie the per-seed order decides; %zu by the per-seed path\n", n, shared.size(), nt,
+                per_seed.size());
+    }
+    if (n == 0) return mtg_fill_batch(idx, p, nullptr, 0, out);
+    if (per_seed.empty()) { *out = rs; rs = nullptr; return MTG_OK; } /* every seed from the table: the records are in seed order already */
+    std::sort(per_seed.begin(), per_seed.end());
+    std::vector<PerSeedPart> parts;
+    struct FreeParts { std::vector<PerSeedPart>& v; ~FreeParts() { for (auto& q : v) if (q.r) mtg_results_free(q.r); } } free_parts{parts};
+    if (int rc = run_per_seed(idx, p, t, seeds, per_seed, parts)) return rc;
+    /* one result set of the two: every record copied, its sequences and extension into the new arenas, target numbers made table numbers */
+    struct Src { const mtg_gap_result* g; const std::vector<uint32_t>* order; };
+    std::vector<Src> src(n, Src{nullptr, nullptr});
+    for (size_t i = 0; i < shared.size(); i++) src[shared[i]] = Src{mtg_results_get(rs, i), nullptr};
+    {
+        size_t q = 0;
+        for (const PerSeedPart& part : parts)
+            for (size_t j = 0; j < part.order.size(); j++, q++) src[per_seed[q]] = Src{mtg_results_get(part.r, j), &part.order[j]};
+    }
+    size_t nfil = 0, seq_bytes = 0, ext_bytes = 1;
+    for (const Src& s : src) {
+        nfil += (size_t)s.g->n_filled;
+        for (int j = 0; j < s.g->n_filled; j++) seq_bytes += strlen(s.g->filled[j].seq) + 1;
+        ext_bytes += s.g->extension ? strlen(s.g->extension) + 1 : 0;
+    }
+    mtg_results* R = results_acquire();
+    struct Guard { mtg_results* r; ~Guard() { if (r) results_release(r); } } guard{R};
+    R->nthreads = p->nb_host_threads;
+    if (!R->ensure(std::max(n, nfil), seq_bytes + 64)) { set_error("no page-locked memory for the results of %zu seeds", n); return MTG_ERR_NOMEM; }
+    R->n = n;
+    R->seq = R->seq_own; R->seq_cap = R->seq_own_cap;
+    R->seq_external = R->seq_on_device = false;
+    if (!R->ext || R->ext_cap < ext_bytes) {
+        pinned_free(R->ext);
+        R->ext_cap = ext_bytes + 4096;
+        R->ext = (char*)pinned_alloc(R->ext_cap);
+        if (!R->ext) { R->ext_cap = 0; set_error("no page-locked memory"); return MTG_ERR_NOMEM; }
+    }
+    R->ext[0] = 0;
+    size_t fo = 0, so = 0, eo = 1;
+    R->n_gaps_filled = 0;
+    for (size_t i = 0; i < n; i++) {
+        const mtg_gap_result& g = *src[i].g;
+        mtg_gap_result& r = R->res[i];
+        r = g;
+        r.filled = R->fil + fo;
+        for (int j = 0; j < g.n_filled; j++) {
+            mtg_filled f = g.filled[j];
+            const size_t len = strlen(f.seq);
+            memcpy(R->seq + so, f.seq, len + 1);
+            f.seq = R->seq + so;
+            so += len + 1;
+            if (src[i].order) f.target_index = (int)(*src[i].order)[(size_t)f.target_index];
+            R->fil[fo++] = f;
+        }
+        if (g.extension && *g.extension) {
+            const size_t len = strlen(g.extension);
+            memcpy(R->ext + eo, g.extension, len + 1);
+            r.extension = R->ext + eo;
+            eo += len + 1;
+        } else r.extension = R->ext;
+        R->n_gaps_filled += g.n_filled > 0;
+    }
+    R->seq_bytes = so;
+    R->in_gap_order = true;
+    guard.r = nullptr;
+    *out = R;
+    return MTG_OK;
+}
 }

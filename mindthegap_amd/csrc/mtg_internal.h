@@ -319,6 +319,16 @@ struct FillInput {
     bool text_mode = false;
     uint64_t n_rwords = 0, n_text_targets = 0, text_bytes = 0;
     const char* text_direct = nullptr; /* text mode: the block lies in memory the caller has page-locked (mtg_host_register): block_c holds the offset arrays only */
+    /* mtg_fill_seeds: every gap's dictionary is the shared table (toff 0, tcnt = its size; encoded keys and piece index resident on the device, nothing
+     * in block C), minus the entries its pattern descriptor lists (block B: see SEED_PATTERN below); the device raises tie_out[g] where the order of the
+     * gap's own dictionary would decide its terminal search */
+    struct Shared {
+        const uint64_t* enc = nullptr; /* le[n] | bad[n] on the device; nullptr: not a seed batch */
+        uint32_t n = 0;
+        const uint32_t* pi = nullptr;  /* piece index: head[pi_mask + 1] | next[4 n] */
+        uint32_t pi_mask = 0;
+    } shared;
+    uint8_t* tie_out = nullptr;        /* host, one byte per gap (seed batches only) */
     static size_t text_block_off(size_t n, size_t nt, int which) /* 0 source_off, 1 pattern_off, 2 dict_seq_off, 3 source_len, 4 dict_seq_len, 5 text */
     {
         const size_t o[6] = {0, 8 * n, 16 * n, 16 * n + 8 * nt, 20 * n + 8 * nt, (20 * n + 12 * nt + 7) & ~(size_t)7};
@@ -550,6 +560,16 @@ enum { MTG_INTERNAL_RETRY_HOST_GENERAL = -1000 }; /* run_general's "do the launc
  * calling thread after everything of the first launch has been queued: the device needs nothing more from the host. */
 int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, ResultSink& sink, DevBatch& special, mtg_batch_stats* stats,
                const std::function<void()>* while_busy = nullptr);
+/* The device side of a shared target table (mtg_fill_seeds), provided by the HIP translation unit through this hook, which it sets in a static
+ * initialiser.  Null in a build without the device code (the emulation): mtg_fill_seeds then takes the per-seed path for every seed. */
+struct SharedTableOps {
+    /* the keys (TARGET_SLOT bytes each) encoded on the device into enc = le[n] | bad[n], and the packed key text copied up */
+    int (*upload)(const mtg_index* idx, const uint8_t* slots, size_t n, const uint64_t* text, size_t text_words, void** enc, void** d_text);
+    /* the piece index of the table for nb_mis (gid 0): head[mask + 1] | next[4 n] */
+    int (*piece_index)(const mtg_index* idx, const void* enc, size_t n, int nb_mis, void** pi, uint32_t* mask);
+    void (*release)(int device, void* p);
+};
+extern SharedTableOps* g_shared_ops;
 /* device copies of a marshalled batch (mtg_batch): block A, block B, encoded targets */
 int batch_upload(const mtg_index* idx, FillInput& in);
 void batch_release_device(FillInput& in);

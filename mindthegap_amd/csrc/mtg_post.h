@@ -68,7 +68,16 @@ struct PostTargets {
     uint32_t pi_mask = 0;
     uint32_t gbase = 0;  /* the number of this gap's first target among the targets of the batch */
     uint32_t gid = 0;    /* the gap's number in the batch */
+    /* a seed of a shared table (mtg_fill_seeds): le / bad are the table, gid 0 keys its piece index, and these entries are not in the seed's
+     * dictionary (SwfPattern's cut triples: entry number at 3 i + 2) */
+    const uint64_t* excl = nullptr;
+    uint32_t n_excl = 0;
 };
+MTG_DEV bool post_excluded(const PostTargets& T, uint32_t t)
+{
+    for (uint32_t i = 0; i < T.n_excl; i++) if (T.excl[3 * i + 2] == t) return true;
+    return false;
+}
 
 /* ---- The piece index (round 6): the terminal search without a pass over the dictionary per contig position.  A contig position matches a target
  * when at most nb_mis of the k nucleotides differ (find_nodes_containing_multiple_R, src/Filler.cpp:1341-1351); cut the k nucleotides into
@@ -200,12 +209,15 @@ enum { POST_TILE = MTG_POST_TILE }; /* words; 512 = 16384 nucleotides */
 
 /* the terminal search of one contig through the piece index: this lane's best key (count << 40 | ORD - (position * n + target)) over the positions
  * lane, lane + 64, ...; the caller takes the wave's maximum.  The contig is read where it lies (a position costs nb_mis + 1 look-ups; its word is the
- * least of it). */
-MTG_DEV_COLD uint64_t post_search_indexed(const PostTargets T, const uint64_t* w, uint32_t L, int k)
+ * least of it).  tie: another target has the count of the lane's best at the same position -- the reference keeps the first of them in ITS
+ * dictionary's order (strict >, src/Filler.cpp:1341-1351), which is what the target number stands for only when the dictionary is the gap's own. */
+MTG_DEV_COLD uint64_t post_search_indexed(const PostTargets T, const uint64_t* w, uint32_t L, int k, bool& tie)
 {
+    tie = false;
     const uint64_t mk = kmask(k), lsb = 0x5555555555555555ULL & mk, ORD = (1ull << 40) - 1;
     const uint32_t np = T.nb_mis + 1u, npos = L - (uint32_t)k + 1;
     uint64_t best = 0;
+    uint32_t best_j = 0;
     for (uint32_t jb = 0; jb < npos; jb += MTG_NLANES) {
         const uint32_t j = jb + MTG_LANE();
         if (j < npos) {
@@ -215,7 +227,7 @@ MTG_DEV_COLD uint64_t post_search_indexed(const PostTargets T, const uint64_t* w
                 uint32_t e = T.pi_head[post_piece_slot((x >> (2u * pb)) & ((1ull << (2u * (pe - pb))) - 1ull), p, T.gid, T.pi_mask)];
                 while (e != (uint32_t)POST_INDEX_NIL) {
                     const uint32_t t = (e >> 2) - T.gbase;
-                    if (t < T.n && (e & 3u) == p) {
+                    if (t < T.n && (e & 3u) == p && !(T.n_excl && post_excluded(T, t))) {
                         const uint64_t m = x ^ T.le[t];
                         const uint64_t mism = ((m | (m >> 1)) & lsb) | T.bad[t];
 #ifdef MTG_EMU
@@ -225,7 +237,9 @@ MTG_DEV_COLD uint64_t post_search_indexed(const PostTargets T, const uint64_t* w
 #endif
                         if (nbm + T.nb_mis >= (uint32_t)k && nbm > 0) {
                             const uint64_t key = ((uint64_t)nbm << 40) | (ORD - ((uint64_t)j * T.n + t));
-                            best = key > best ? key : best;
+                            /* (a target is met once per piece without a difference: the same key again is not a tie) */
+                            if (key > best) { tie = best != 0 && (key >> 40) == (best >> 40) && best_j == j; best = key; best_j = j; }
+                            else if (key != best && (key >> 40) == (best >> 40) && best_j == j) tie = true;
                         }
                     }
                     e = T.pi_next[e];
@@ -239,8 +253,9 @@ MTG_DEV_COLD uint64_t post_search_indexed(const PostTargets T, const uint64_t* w
 
 /* hist: 256 zeroed counters shared by the lanes; tile: POST_TILE + 2 words; blk: 64 words (all LDS on the device) */
 /* dbg (timing experiments only, never set by the product): bit 0 = no coverage pass, bit 1 = no terminal search */
+/* tie_out (seeds of a shared table): set to 1 when the terminal search of a contig met a tie that the seed's own dictionary order would decide */
 MTG_DEV void post_gap(const Index& ix, const FillCfg& cfg, const GapScratch& S, const GapOut& o, const PostTargets& T, uint32_t* hist, uint64_t* tile, uint64_t* blk, PostOut& out,
-                      uint32_t dbg = 0)
+                      uint32_t dbg = 0, uint8_t* tie_out = nullptr)
 {
     const int k = ix.k;
     const uint64_t mk = kmask(k);
@@ -309,7 +324,9 @@ MTG_DEV void post_gap(const Index& ix, const FillCfg& cfg, const GapScratch& S, 
                 if (j_hi >= npos) break;
             }
         }
-        if (indexed && L >= (uint32_t)k) best = post_search_indexed(T, w, L, k); /* a call: the pass below keeps the registers it had before the index existed */
+        bool tie = false;
+        uint64_t mine = 0;
+        if (indexed && L >= (uint32_t)k) best = mine = post_search_indexed(T, w, L, k, tie); /* a call: the pass below keeps the registers it had before the index existed */
         else if (!have_exact && L >= (uint32_t)k && T.n) {
             const uint32_t npos = L - (uint32_t)k + 1, nwc = (L + 31) / 32;
             for (uint32_t ws = 0; ws < nwc; ws += POST_TILE) {
@@ -348,12 +365,14 @@ MTG_DEV void post_gap(const Index& ix, const FillCfg& cfg, const GapScratch& S, 
             }
         }
         if (!have_exact) best = wave_max64(best);
+        if (tie_out && indexed && wave_any(tie && best != 0 && mine == best)) *tie_out = 1; /* the lane that holds the winner saw a tie at its position */
 #ifdef MTG_XCHECK /* TEST-ONLY: the pass over every target finds the same arg-max as the piece index */
         if (indexed && L >= (uint32_t)k) {
             uint64_t want = 0;
             for (uint32_t j = 0; j + (uint32_t)k <= L && (uint32_t)(want >> 40) != (uint32_t)k; j++) {
                 const uint64_t x = le_kmer(w, j, mk);
                 for (uint32_t t = 0; t < T.n; t++) {
+                    if (T.n_excl && post_excluded(T, t)) continue;
                     const uint64_t m = x ^ T.le[t];
                     const uint32_t nbm = (uint32_t)k - (uint32_t)__builtin_popcountll(((m | (m >> 1)) & lsb) | T.bad[t]);
                     if (nbm + T.nb_mis >= (uint32_t)k && nbm > 0) { const uint64_t key = ((uint64_t)nbm << 40) | (ORD - ((uint64_t)j * T.n + t)); want = key > want ? key : want; }

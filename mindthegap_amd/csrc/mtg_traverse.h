@@ -2153,8 +2153,40 @@ struct SwfPattern {
     const uint64_t* words;
     uint32_t rlen;
     uint64_t r0;
+    /* a seed of a shared table (mtg_fill_seeds): words is the table's key text and R is that text with these spans cut out -- ncut triples
+     * (first nucleotide, length, entry number), ascending */
+    const uint64_t* cut = nullptr;
+    uint32_t ncut = 0;
 };
-MTG_DEV uint32_t packed_nt(const uint64_t* w, uint32_t i) { return (uint32_t)(w[i >> 5] >> (2 * (i & 31))) & 3u; }
+MTG_DEV uint32_t packed_nt(const uint64_t* w, uint64_t i) { return (uint32_t)(w[i >> 5] >> (2 * (i & 31))) & 3u; }
+
+/* A seed's pattern in block B: roff[g] has SEED_PATTERN set, and the words at roff[g] & ~SEED_PATTERN are
+ *   [0] the device address of the table's key text, [1] ncut, [2 + 3i, 3 + 3i, 4 + 3i] cut i (see SwfPattern). */
+enum : uint32_t { SEED_PATTERN = 0x80000000u };
+MTG_DEV SwfPattern swf_pattern(const uint64_t* rwords, const uint32_t* roff, const uint32_t* rlen, const uint64_t* r0, uint32_t g)
+{
+    SwfPattern R;
+    const uint32_t o = roff[g];
+    R.rlen = rlen[g];
+    R.r0 = r0[g];
+    if (o & SEED_PATTERN) {
+        const uint64_t* d = rwords + (o & ~SEED_PATTERN);
+        R.words = (const uint64_t*)d[0];
+        R.ncut = (uint32_t)d[1];
+        R.cut = d + 2;
+    } else R.words = rwords + o;
+    return R;
+}
+/* nucleotide j of R: its place in the key text is j plus the lengths of the spans cut out before it */
+MTG_DEV uint32_t pattern_nt(const SwfPattern& R, uint32_t j)
+{
+    uint64_t t = j;
+    for (uint32_t c = 0; c < R.ncut; c++) {
+        if (R.cut[3 * c] > t) break;
+        t += R.cut[3 * c + 1];
+    }
+    return packed_nt(R.words, t);
+}
 
 /* does the contig contain R literally (strstr at IterativeExtensions [MEM]) */
 MTG_DEV_NOINLINE bool contig_contains(const uint64_t* wd, uint32_t clen, const SwfPattern& R)
@@ -2163,7 +2195,7 @@ MTG_DEV_NOINLINE bool contig_contains(const uint64_t* wd, uint32_t clen, const S
     if (R.rlen > clen) return false;
     for (uint32_t p = 0; p + R.rlen <= clen; p++) {
         bool ok = true;
-        for (uint32_t j = 0; j < R.rlen && ok; j++) ok = packed_nt(wd, p + j) == packed_nt(R.words, j);
+        for (uint32_t j = 0; j < R.rlen && ok; j++) ok = packed_nt(wd, p + j) == (R.ncut ? pattern_nt(R, j) : packed_nt(R.words, j));
         if (ok) return true;
     }
     return false;

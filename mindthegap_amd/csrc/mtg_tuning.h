@@ -55,6 +55,7 @@
     X(CLI_IN_FLIGHT, "", "cap", "the tool: worker threads per device (default 3, at most 6)") \
     X(CLI_WRITERS, "1", "cap", "the tool: writer threads per output file (a file's lock serialises write(2): more than one per file was measured the same or slower)") \
     X(CLI_NO_MMAP, "", "test", "the tool reads its breakpoint file instead of mapping it") \
+    X(CONTIG_PER_SEED, "", "ab", "contig mode (the tool and mtg_fill_seeds): every seed gets its own copy of the dictionary (mtg_fill_batch, as until round 6) instead of the shared table on the device") \
     X(HOST_FORMAT, "", "ab", "the tool: every site's text by the host's writers (round 3) instead of the device's formatter") \
     X(TOOL_TIMERS, "", "diag", "the tool: where the time of a run went (stderr)") \
     X(TOOL_QUIET, "", "diag", "the tool: no summary on stdout")

@@ -199,6 +199,11 @@ def _bind(lib):
     lib.mtg_fill_main.argtypes = [C.c_int, P(C.c_char_p)]
     lib.mtg_fill_main_on_index.argtypes = [C.c_void_p, C.c_int, P(C.c_char_p)]
     lib.mtg_nw_matches.argtypes = [P(C.c_char_p), P(C.c_char_p), C.c_size_t, P(C.c_uint32)]
+    lib.mtg_targets_create.argtypes = [C.c_void_p, P(C.c_char_p), P(C.c_char_p), P(C.c_uint8), C.c_size_t, P(C.c_void_p)]
+    lib.mtg_targets_free.argtypes = [C.c_void_p]
+    lib.mtg_targets_free.restype = None
+    lib.mtg_targets_device_bytes.argtypes = [C.c_void_p, P(C.c_uint64)]
+    lib.mtg_fill_seeds.argtypes = [C.c_void_p, P(Params), C.c_void_p, P(CSeed), C.c_size_t, P(C.c_void_p)]
     lib.mtg_bench_random_lines.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, P(C.c_double), P(C.c_double)]
     return lib
 
@@ -224,6 +229,56 @@ class Gap:
         self.source, self.target = source, target
         self.targets = list(targets)  # [(kmer, name, is_rc)] in dictionary iteration order
         self.is_anchor_repeated, self.reverse = is_anchor_repeated, reverse
+
+
+class CSeed(C.Structure):
+    _fields_ = [("source", C.c_char_p), ("excluded", C.POINTER(C.c_uint32)), ("n_excluded", C.c_uint32), ("is_anchor_repeated", C.c_int), ("reverse", C.c_int)]
+
+
+class Seed:
+    """One seed of contig mode (contigFunctor, src/Filler.cpp:492-572): its source and the table entries its own dictionary leaves out."""
+
+    def __init__(self, source, excluded=(), is_anchor_repeated=False, reverse=False):
+        self.source = source
+        self.excluded = sorted(int(e) for e in excluded)
+        self.is_anchor_repeated, self.reverse = is_anchor_repeated, reverse
+
+
+class Targets:
+    """The dictionary of all targets of a contig-mode job, resident on the device of the index that made it (Index.targets)."""
+
+    def __init__(self, lib, handle, n):
+        self.lib, self.h, self.n = lib, handle, n
+
+    def device_bytes(self):
+        b = C.c_uint64()
+        _check(self.lib.mtg_targets_device_bytes(self.h, C.byref(b)))
+        return int(b.value)
+
+    def close(self):
+        if self.h:
+            self.lib.mtg_targets_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _results_dicts(lib, h, n):
+    res = []
+    for i in range(n):
+        r = lib.mtg_results_get(h, i).contents
+        filled = []
+        for j in range(r.n_filled):
+            f = r.filled[j]
+            filled.append(dict(seq=f.seq.decode(), nb_errors_in_anchor=f.nb_errors_in_anchor, target_index=f.target_index, avg_coverage=f.avg_coverage,
+                               median_coverage=f.median_coverage, qual=f.qual, solution_count=f.solution_count, solution_rank=f.solution_rank))
+        res.append(dict(nb_nodes=r.nb_nodes, total_nt=r.total_nt, nb_terminal=r.nb_terminal, has_solution_counts=bool(r.has_solution_counts),
+                        nb_total_filled=r.nb_total_filled, nb_reported=r.nb_reported, filled=filled, extension=r.extension.decode()))
+    return res
 
 
 class CTextGaps(C.Structure):
@@ -545,6 +600,36 @@ class Index:
                             nb_total_filled=r.nb_total_filled, nb_reported=r.nb_reported, filled=filled, extension=r.extension.decode()))
         self.lib.mtg_results_free(h)
         return res
+
+    def targets(self, entries):
+        """mtg_targets_create: the dictionary of all targets, entries (key, name, is_rc) in its iteration order, uploaded once."""
+        entries = list(entries)
+        n = len(entries)
+        keys = (C.c_char_p * max(n, 1))(*[e[0].encode() for e in entries])
+        names = (C.c_char_p * max(n, 1))(*[e[1].encode() for e in entries])
+        rcs = (C.c_uint8 * max(n, 1))(*[1 if e[2] else 0 for e in entries])
+        h = C.c_void_p()
+        _check(self.lib.mtg_targets_create(self.h, keys, names, rcs, n, C.byref(h)))
+        return Targets(self.lib, h, n)
+
+    def fill_seeds(self, targets, seeds, params=None):
+        """mtg_fill_seeds: every seed against the table without its excluded entries; the same dicts as fill_batch, except that target_index is a
+        table entry number."""
+        params = params or FillParams()
+        n = len(seeds)
+        arr = (CSeed * max(n, 1))()
+        keep = []
+        for i, s in enumerate(seeds):
+            ex = (C.c_uint32 * max(len(s.excluded), 1))(*s.excluded)
+            src = s.source.encode()
+            keep.append((ex, src))
+            arr[i] = CSeed(src, ex, len(s.excluded), int(s.is_anchor_repeated), int(s.reverse))
+        h = C.c_void_p()
+        _check(self.lib.mtg_fill_seeds(self.h, C.byref(params.c), targets.h, arr, n, C.byref(h)))
+        try:
+            return _results_dicts(self.lib, h, n)
+        finally:
+            self.lib.mtg_results_free(h)
 
     def close(self):
         if self.h:
