@@ -227,6 +227,14 @@ MTG_DEV void atomic_or64(uint64_t* p, uint64_t bits)
     atomicOr(reinterpret_cast<unsigned long long*>(p), (unsigned long long)bits);
 #endif
 }
+MTG_DEV void atomic_or32(uint32_t* p, uint32_t bits)
+{
+#ifdef MTG_EMU
+    __sync_fetch_and_or(p, bits);
+#else
+    atomicOr(p, bits);
+#endif
+}
 
 /* insert key with value bits, OR-ing into an existing entry.  Returns 0 (entry existed), 2 (entry created), or
  * 1 when the key would be displaced by more than MTG_MAX_DISP buckets (the host then rebuilds with more buckets). */

@@ -71,9 +71,22 @@ MTG_DEV uint32_t codes16(const uint64_t* w, uint32_t i)
     return (uint32_t)v;
 }
 
+/* The tail of a batch's sequence arena in 2-bit form (the packed link path: the host expands it into the arena, mtg_hostutil.h: expand_codes).
+ * Arena bytes [x, end) are codes, byte x + i at bits 2 (i % 16) of half[i / 16] (two halves = the shadow's 64-bit word (i / 32)), a NUL as
+ * code 0; bytes below x stay ASCII.  x is a multiple of 32, so an aligned 16-byte piece is one half and a ragged end lies inside one:
+ * whole halves are plain stores, the ends of neighbouring fills are OR-ed into a half the host zeroed for the launch.  half == nullptr:
+ * everything ASCII. */
+struct PackedTail {
+    uint32_t* half;
+    uint64_t x, cap; /* split point (arena offset); halves of the buffer */
+};
+/* the split point of an arena of `end` bytes of which the share q / 65536 crosses packed: round_down_32((1 - q / 65536) * end) */
+MTG_HD uint64_t packed_split(uint64_t end, uint32_t q) { return ((end * (65536ull - q)) >> 16) & ~31ull; }
+
 /* dst[0, L) = ASCII of src nucleotides [from, from + L), reverse-complemented when rc; dst[L] = 0.  The lanes of a wave write aligned
- * 16-byte pieces of the destination (byte stores at the ragged ends), so the arena needs no padding between sequences. */
-template <uint32_t GW> MTG_DEV void emit_ascii_g(const uint64_t* src, uint32_t from, uint32_t L, bool rc, char* dst, uint32_t lane)
+ * 16-byte pieces of the destination (byte stores at the ragged ends), so the arena needs no padding between sequences.  With a packed tail
+ * (aoff: dst's offset in the arena, whose base is 64-byte aligned) the pieces from pk.x on are written as codes instead. */
+template <uint32_t GW> MTG_DEV void emit_ascii_g(const uint64_t* src, uint32_t from, uint32_t L, bool rc, char* dst, uint32_t lane, const PackedTail& pk = PackedTail{nullptr, 0, 0}, uint64_t aoff = 0)
 {
     const uint64_t d0 = (uint64_t)(uintptr_t)dst;
     const uint32_t head = (uint32_t)((16u - (d0 & 15u)) & 15u); /* bytes before the first aligned piece */
@@ -91,6 +104,16 @@ template <uint32_t GW> MTG_DEV void emit_ascii_g(const uint64_t* src, uint32_t f
             const uint32_t got = hi - lo + 1u;
             codes = rev_fields32(codes16(src, lo)) >> (2u * (16u - got)); /* nucleotide hi first */
         }
+        const uint64_t a = aoff + o0;
+        if (pk.half && a >= pk.x) { /* the codes of the output characters, as ascii16 spells them (complement: code ^ 2) */
+            const uint64_t h = (a - pk.x) >> 4;
+            const uint32_t oc = rc ? codes ^ 0xAAAAAAAAu : codes;
+            if (h < pk.cap) {
+                if (n == 16u) pk.half[h] = oc; /* aligned: the half is this piece's alone */
+                else atomic_or32(pk.half + h, (oc & ((1u << (2u * n)) - 1u)) << (2u * (uint32_t)(a & 15u)));
+            }
+            continue;
+        }
         uint32_t out[4];
         ascii16(codes, rc, out);
         char* d = dst + o0;
@@ -103,7 +126,7 @@ template <uint32_t GW> MTG_DEV void emit_ascii_g(const uint64_t* src, uint32_t f
             for (uint32_t b = 0; b < n; b++) d[b] = (char)((out[b >> 2] >> (8u * (b & 3u))) & 0xFFu);
         }
     }
-    if (lane == 0) dst[L] = 0;
+    if (lane == 0 && !(pk.half && aoff + L >= pk.x)) dst[L] = 0; /* a packed NUL is code 0, put back by the host */
 }
 /* by the lanes of a wave (one lane in the emulation) */
 MTG_DEV void emit_ascii(const uint64_t* src, uint32_t from, uint32_t L, bool rc, char* dst) { emit_ascii_g<MTG_NLANES>(src, from, L, rc, dst, MTG_LANE()); }
@@ -129,7 +152,12 @@ struct EmitDev {
     uint64_t wire_cap, wire_tag;
     const PartTot* tot;  /* the launch's totals (device memory, complete before k_emit starts) */
     uint32_t wire_gaps;  /* gaps of the batch */
+    /* the packed tail of the sequence arena (PackedTail): halves zeroed by the host, their number, the share in 65536ths; nullptr = all ASCII */
+    uint32_t* shadow = nullptr;
+    uint64_t shadow_cap = 0;
+    uint32_t pack_q = 0;
 };
+MTG_DEV PackedTail packed_tail(const EmitDev& D) { return PackedTail{D.shadow, D.shadow ? packed_split(D.tot->end[2], D.pack_q) : 0ull, D.shadow_cap}; }
 /* where the sections of a relocatable batch begin */
 struct WireLayout {
     uint64_t o_gaps, o_filled, o_seq, o_ext, total;
@@ -192,7 +220,7 @@ template <uint32_t GW> MTG_DEV void emit_lean(const UStore& us, const FillCfg& c
         const int64_t x0 = (int64_t)(32ull * s_cstart(cfg, S)[0]) + k;
         const bool bwd = (cm.src & 1ull) != 0;
         const uint64_t from = bwd ? cmd_store_nt(cm, x0 + (int64_t)L - 1) : cmd_store_nt(cm, x0);
-        emit_ascii_g<GW>(us.words + (from >> 5), (uint32_t)(from & 31ull), L, bwd ? !reverse : reverse, D.seq + abase, gl);
+        emit_ascii_g<GW>(us.words + (from >> 5), (uint32_t)(from & 31ull), L, bwd ? !reverse : reverse, D.seq + abase, gl, packed_tail(D), abase);
     }
     if (gl != 0) return;
     mtg_gap_result g;
@@ -230,8 +258,8 @@ MTG_DEV void emit_gap(const UStore& us, const FillCfg& cfg, const GapScratch& S,
         const int64_t x0 = (int64_t)(32ull * s_cstart(cfg, S)[0]) + k;
         const bool bwd = (cm.src & 1ull) != 0;
         const uint64_t from = bwd ? cmd_store_nt(cm, x0 + (int64_t)L - 1) : cmd_store_nt(cm, x0);
-        emit_ascii(us.words + (from >> 5), (uint32_t)(from & 31ull), L, bwd ? !reverse : reverse, seq_arena + r.abase);
-    } else if (seq_ok) emit_ascii(w, (uint32_t)k, r.asc - 1u, reverse, seq_arena + r.abase);
+        emit_ascii_g<MTG_NLANES>(us.words + (from >> 5), (uint32_t)(from & 31ull), L, bwd ? !reverse : reverse, seq_arena + r.abase, lane, packed_tail(D), r.abase);
+    } else if (seq_ok) emit_ascii_g<MTG_NLANES>(w, (uint32_t)k, r.asc - 1u, reverse, seq_arena + r.abase, lane, packed_tail(D), r.abase);
     if (ext_ok) emit_ascii(w, (uint32_t)k, r.ext - 1u, false, D.ext + r.ebase);
     if (wire_ok && r.ext) emit_ascii(w, (uint32_t)k, r.ext - 1u, false, (char*)D.wire + wl.o_ext + r.ebase);
     /* the dense arrays are sized by the last need and k_emit runs before the launch's totals are known: a gap that does not fit writes

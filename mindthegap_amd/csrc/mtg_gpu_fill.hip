@@ -788,7 +788,7 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
     int ws_next = 0;
     auto wsbuf = [&]() { WsBuf b; b.ws = &ws; b.slot = ws_next++; return b; };
     WsBuf d_ina = wsbuf(), d_inb = wsbuf(), d_inc = wsbuf(), d_tenc = wsbuf(), d_ilv = wsbuf(), d_zero = wsbuf(), d_raw = wsbuf(), d_out = wsbuf(), d_rec = wsbuf(), d_ids = wsbuf(), d_dw = wsbuf(),
-          d_dm = wsbuf(), d_combo = wsbuf(), d_blocks = wsbuf(), d_seq = wsbuf(), d_ext = wsbuf(), d_res = wsbuf(), d_fil = wsbuf(), d_tot = wsbuf(), d_rlist = wsbuf(), d_glist = wsbuf(), d_paths = wsbuf(), d_park = wsbuf(), d_ggaps = wsbuf(), d_gsols = wsbuf(), d_gascii = wsbuf(), d_gtmp = wsbuf(), d_gbnd = wsbuf(), d_head = wsbuf(), d_pidx = wsbuf(), d_tie = wsbuf();
+          d_dm = wsbuf(), d_combo = wsbuf(), d_blocks = wsbuf(), d_seq = wsbuf(), d_ext = wsbuf(), d_res = wsbuf(), d_fil = wsbuf(), d_tot = wsbuf(), d_rlist = wsbuf(), d_glist = wsbuf(), d_paths = wsbuf(), d_park = wsbuf(), d_ggaps = wsbuf(), d_gsols = wsbuf(), d_gascii = wsbuf(), d_gtmp = wsbuf(), d_gbnd = wsbuf(), d_head = wsbuf(), d_pidx = wsbuf(), d_tie = wsbuf(), d_shadow = wsbuf();
     /* the marshalled input: three blocks, three copies; the targets (block C, text) become k-mers and masks on the device.  A batch that
      * was prepared ahead (mtg_batch) is resident already */
     double t0 = now_ms();
@@ -923,6 +923,8 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
     HIP_TRY(events.make(ev0));
     HIP_TRY(events.make(ev2));
     HIP_TRY(events.make(ev3));
+    hipEvent_t evp; /* the records and the packed tail of the sequence arena are on the host */
+    HIP_TRY(events.make(evp));
     if (ktimers) {
         HIP_TRY(events.make(eve));
         HIP_TRY(events.make(evc));
@@ -1141,6 +1143,17 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
             HIP_TRY(hipGetLastError());
             EmitDev D;
             EmitHost H;
+            /* The packed link path (PACKED_SEQ_SHARE of the tuning table): a whole-batch launch whose results cross in one block sends the tail of
+             * its sequence arena as 2-bit codes (mtg_emit.h: PackedTail), a quarter of the bytes; the host expands them while the ASCII head is on
+             * the link.  Every other launch, and the emission again after an arena grew, writes ASCII only. */
+            const double share = std::min(1.0, std::max(0.0, tune::f(tune::T_PACKED_SEQ_SHARE, 0.0)));
+            const uint32_t pack_q = (uint32_t)std::lround(share * 65536.0);
+            bool packed = want_records && combo && identity && arena_used[0] == 0 && pack_q != 0; /* = one_copy below */
+            uint64_t shadow_halves = 0;
+            if (packed) {
+                shadow_halves = 2 * ((((uint64_t)sink.seq_cap * pack_q) >> 16) / 32 + 3); /* the tail of a full arena, rounded out */
+                HIP_TRY(d_shadow.alloc(shadow_halves * 4));
+            }
             auto emit = [&]() -> int {
                 D.seq = sink.seq_dev ? sink.seq_dev : p_seq(); D.ext = d_ext.as<char>();
                 D.seq_cap = sink.seq_cap; D.ext_cap = sink.ext_cap;
@@ -1150,6 +1163,8 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
                 const bool want_wire = sink.wire_dev != nullptr && identity && tier == 0;
                 D.wire = want_wire ? (uint8_t*)sink.wire_dev : nullptr; D.wire_cap = sink.wire_cap; D.wire_tag = sink.wire_tag;
                 D.tot = d_tot.as<PartTot>(); D.wire_gaps = m;
+                D.shadow = packed ? d_shadow.as<uint32_t>() : nullptr; D.shadow_cap = shadow_halves; D.pack_q = pack_q;
+                if (packed) HIP_TRY(hipMemsetAsync(d_shadow.p, 0, shadow_halves * 4, stream));
                 if (want_wire) HIP_TRY(hipMemsetAsync(sink.wire_dev, 0, sizeof(mtg_wire_header), stream)); /* no header, no payload (k_wire_sum) */
                 H.seq = sink.seq; H.ext = sink.ext; H.fil = sink.fil;
                 if (!want_wire)
@@ -1210,6 +1225,7 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
                 /* k_emit made the records' offsets absolute: run the layout again from the launch's begin */
                 hipLaunchKernelGGL(k_scan1, dim3(nblocks), dim3(SCAN_SL), 0, stream, d_rec.as<SlotRec>(), m, d_blocks.as<ScanBlock>());
                 hipLaunchKernelGGL(k_scan2, dim3(1), dim3(256), 0, stream, d_blocks.as<ScanBlock>(), nblocks, sbegin, d_tot.as<PartTot>(), (PartTot*)nullptr, park);
+                packed = false;
                 if (int erc = emit()) return erc;
             }
             /* bring the launch's results to the host.  Result copies of six batches at once share the link worse than two or three do
@@ -1218,8 +1234,20 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
             std::vector<mtg_gap_result> tmp_res;
             std::vector<mtg_filled> tmp_fil;
             const bool one_copy = combo && identity && tot.begin[2] == 0; /* records, filled records and sequences of the launch: one block on both sides */
+            /* packed: (a) the records and the codes of the arena's tail, (b) its ASCII head [0, x), which is on the link while the host expands (a) */
+            const uint64_t pack_x = packed ? packed_split(tot.end[2], pack_q) : 0, pack_words = packed ? (tot.end[2] - pack_x + 31) / 32 : 0;
+            uint64_t* h_shadow = nullptr;
+            if (packed) { /* implies one_copy and want_records */
+                h_shadow = (uint64_t*)staging_host(&ws, Workspace::NHOST - 3, pack_words * 8 + 64);
+                if (!h_shadow) { set_error("no page-locked memory for the packed sequences of a launch"); return MTG_ERR_NOMEM; }
+            }
             if (want_records) {
-                if (one_copy) HIP_TRY(hipMemcpyAsync(sink.combo, d_combo.p, sink.combo_off_seq + (size_t)tot.end[2], hipMemcpyDeviceToHost, stream));
+                if (h_shadow) {
+                    HIP_TRY(hipMemcpyAsync(sink.combo, d_combo.p, sink.combo_off_seq, hipMemcpyDeviceToHost, stream));
+                    if (pack_words) HIP_TRY(hipMemcpyAsync(h_shadow, d_shadow.p, pack_words * 8, hipMemcpyDeviceToHost, stream));
+                    HIP_TRY(hipEventRecord(evp, stream));
+                    if (pack_x) HIP_TRY(hipMemcpyAsync(sink.combo + sink.combo_off_seq, (const char*)d_combo.p + sink.combo_off_seq, pack_x, hipMemcpyDeviceToHost, stream));
+                } else if (one_copy) HIP_TRY(hipMemcpyAsync(sink.combo, d_combo.p, sink.combo_off_seq + (size_t)tot.end[2], hipMemcpyDeviceToHost, stream));
                 else if (identity) {
                     HIP_TRY(hipMemcpyAsync(sink.res, p_res(), (size_t)m * sizeof(mtg_gap_result), hipMemcpyDeviceToHost, stream));
                     HIP_TRY(hipMemcpyAsync(sink.fil, p_fil(), (size_t)m * sizeof(mtg_filled), hipMemcpyDeviceToHost, stream));
@@ -1286,6 +1314,14 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
                 if (!dev_general) { if (int crc = contigs_to_host()) return crc; }
             }
             HIP_TRY(hipEventRecord(ev3, stream));
+            if (h_shadow) {
+                /* before anything the host writes itself goes into the arena (multi-contig gaps, re-runs) */
+                HIP_TRY(hipEventSynchronize(evp));
+                const double tx = now_ms();
+                expand_packed_tail(h_shadow, sink.seq, pack_x, tot.end[2], sink.res, sink.fil, n, std::min(8, std::max(1, Pool::cpu_budget() / 2)));
+                if (dbg) fprintf(stderr, "  [device_run] %-18s %.3f ms (%llu of %llu arena bytes from %llu words)\n", "packed tail", now_ms() - tx,
+                                 (unsigned long long)(tot.end[2] - pack_x), (unsigned long long)tot.end[2], (unsigned long long)pack_words);
+            }
             HIP_TRY(hipEventSynchronize(ev3));
             copy_turn.release();
             st.d2h_ms += now_ms() - t0;

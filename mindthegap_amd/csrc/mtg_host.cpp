@@ -509,6 +509,65 @@ inline bool all_upper_acgt(const char* s, size_t n)
 }
 } // namespace
 
+void expand_codes_scalar(const uint64_t* w, size_t b, size_t e, char* out)
+{
+    static const char NT[4] = {'A', 'C', 'T', 'G'};
+    for (size_t i = b; i < e; i++) out[i] = NT[(w[i >> 5] >> (2 * (i & 31))) & 3];
+}
+#if defined(__x86_64__)
+/* 32 letters a step: byte i of the word goes to output bytes 4i .. 4i + 3, each keeps its own two bits (masks 0x03 0x0C 0x30 0xC0), the upper
+ * nibble is folded onto the lower one, and a 16-entry table turns {0,1,2,3} and {0,4,8,12} into letters */
+__attribute__((target("avx2"))) static void expand_codes_avx2(const uint64_t* w, size_t b, size_t e, char* out)
+{
+    size_t i = b;
+    const size_t head = std::min(e, (b + 31) & ~(size_t)31);
+    expand_codes_scalar(w, i, head, out);
+    i = head;
+    const __m256i spread = _mm256_setr_epi8(0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 6, 6, 6, 6, 7, 7, 7, 7);
+    const __m256i field = _mm256_set1_epi32((int)0xC0300C03u), low = _mm256_set1_epi8(0x0F);
+    const __m256i lut = _mm256_setr_epi8('A', 'C', 'T', 'G', 'C', 0, 0, 0, 'T', 0, 0, 0, 'G', 0, 0, 0, 'A', 'C', 'T', 'G', 'C', 0, 0, 0, 'T', 0, 0, 0, 'G', 0, 0, 0);
+    for (; i + 32 <= e; i += 32) {
+        __m256i t = _mm256_and_si256(_mm256_shuffle_epi8(_mm256_set1_epi64x((long long)w[i >> 5]), spread), field);
+        t = _mm256_and_si256(_mm256_or_si256(t, _mm256_srli_epi16(t, 4)), low);
+        _mm256_storeu_si256(reinterpret_cast<__m256i*>(out + i), _mm256_shuffle_epi8(lut, t));
+    }
+    expand_codes_scalar(w, i, e, out);
+}
+static const bool have_avx2 = __builtin_cpu_supports("avx2") && !tune::on(tune::T_NO_VEC);
+#endif
+void expand_codes(const uint64_t* w, size_t b, size_t e, char* out)
+{
+#if defined(__x86_64__)
+    if (have_avx2) { expand_codes_avx2(w, b, e, out); return; }
+#endif
+    expand_codes_scalar(w, b, e, out);
+}
+
+void expand_packed_tail(const uint64_t* w, char* seq, uint64_t x, uint64_t end, const mtg_gap_result* res, const mtg_filled* fil, size_t n, int nthreads)
+{
+    if (end <= x || n == 0) return;
+    /* pieces of the gap range: a piece owns the bytes from its first fill's start to the next piece's first fill's start (the last one: to
+     * end), so that the byte before a fill's start -- its predecessor's NUL -- is written by the piece that expanded it */
+    const size_t pieces = std::min<size_t>(n, 256);
+    auto first_fill = [&](size_t g, size_t lim) { while (g < lim && res[g].n_filled == 0) g++; return g; };
+    auto start_of = [&](size_t g) { return (uint64_t)(fil[g].seq - seq); };
+    parallel_for(pieces, nthreads, [&](size_t c) {
+        const size_t g0 = n * c / pieces, g1 = n * (c + 1) / pieces;
+        const size_t f = first_fill(g0, g1);
+        if (f == g1) return; /* no fill starts in the piece: it owns no byte */
+        const size_t nf = first_fill(g1, n);
+        const uint64_t lo = std::max<uint64_t>(start_of(f), x), hi = std::min<uint64_t>(nf < n ? start_of(nf) : end, end);
+        if (hi <= lo) return;
+        expand_codes(w, lo - x, hi - x, seq + x);
+        for (size_t g = f + 1; g < g1; g++) {
+            if (res[g].n_filled == 0) continue;
+            const uint64_t z = start_of(g) - 1;
+            if (z >= lo && z < hi) seq[z] = 0;
+        }
+        seq[hi - 1] = 0;
+    }, 1);
+}
+
 void FillInput::set_common(size_t g, std::string_view source, std::string_view swf_target, int nb_mis, uint8_t gap_flags)
 {
     flags[g] = gap_flags;

@@ -275,6 +275,14 @@ struct TargetSpan {
 
 /* grow-only staging block `slot` of a workspace (page-locked on the device build); nullptr when it cannot be had */
 void* staging_host(Workspace* ws, int slot, size_t bytes);
+/* The packed tail of a whole-batch launch's sequence arena (mtg_emit.h: PackedTail) back to ASCII.  expand_codes: out[i] = the letter of code
+ * i of w (code i of word i / 32 at bits 2 (i % 32); A C T G = 0 1 2 3) for i in [b, e) -- AVX2 where the CPU has it (not under NO_VEC),
+ * expand_codes_scalar the plain form.  expand_packed_tail: arena bytes [x, end) of seq from the shadow w (its byte 0 = arena byte x), and the
+ * NULs among them put back -- one before every fill's start, and at end - 1 -- from the records of the batch's n gaps (dense, in gap order:
+ * res[g].n_filled != 0 <=> fil[g].seq is a fill of the arena); over the worker pool, nthreads at most. */
+void expand_codes(const uint64_t* w, size_t b, size_t e, char* out);
+void expand_codes_scalar(const uint64_t* w, size_t b, size_t e, char* out);
+void expand_packed_tail(const uint64_t* w, char* seq, uint64_t x, uint64_t end, const mtg_gap_result* res, const mtg_filled* fil, size_t n, int nthreads);
 /* page-locked host memory for the result arrays of a batch (plain memory in the emulation); nullptr on failure */
 void* pinned_alloc(size_t bytes);
 void pinned_free(void* p);

@@ -24,6 +24,7 @@
 /* X(name, default, kind, what) */
 #define MTG_TUNABLES(X) \
     X(POOL_THREADS, "", "cap", "size of the host worker pool (default: the CPUs the process may use -- hardware threads, affinity mask, cgroup quota -- at most 64); read when the pool starts") \
+    X(PACKED_SEQ_SHARE, "0.75", "cap", "share (0..1) of a whole-batch launch's sequence arena that crosses the link 2-bit packed, the host expanding it to ASCII (0: every byte as ASCII)") \
     X(COPY_SLOTS, "3", "cap", "batches of a device that copy their results to the host at the same time (0: no limit); more copies at once share the link worse") \
     X(UPLOAD_OWN_STREAM, "", "ab", "every batch uploads its input on its own stream instead of the device's one upload stream (three uploads at a time take the link from the downloads: profiles/r04_text_entry.txt)") \
     X(SPARSE_ADJ_LOAD, "0.49", "cap", "load factor of the sparse junction table, as a share of the dense one's; 0.7 overflows the displacement range at human scale") \
@@ -48,7 +49,7 @@
     X(DEBUG_SKIP_FINISH, "", "diag", "parked gaps stay parked (and fail as overflowing gaps)") \
     X(KERNEL_TIMERS, "", "diag", "every batch records an event between its kernels and mtg_last_batch_stats carries each kernel's own time (off: three events per batch instead of nine, only device_span_ms)") \
     X(DEBUG_TIMERS, "", "diag", "per-phase wall times of every batch and every index construction on stderr") \
-    X(NO_VEC, "", "test", "scalar instead of pext host code in the input pass") \
+    X(NO_VEC, "", "test", "scalar instead of vector host code (pext in the input pass, AVX2 in the expansion of a packed arena)") \
     X(NO_PREFETCH, "", "test", "no software prefetch in the input pass") \
     X(NB_GPUS, "", "cap", "the tool: devices to use (default: all visible; -nb-gpus overrides)") \
     X(CLI_BATCH, "", "cap", "the tool: sites per batch (default 100 000)") \
