@@ -2180,6 +2180,7 @@ int index_from_stream(ReadStream& rs, int k, int abundance_min, int abundance_ma
             /* the lean build: the solid k-mers' junctions into the junction table; their abundances stay in the count table (one counting
              * pass) or go into an ABND table of their own (several: the count table of a pass does not outlive it) */
             prof.host_phase("count_reads", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - prof.t0).count(), 0, n_solid);
+            prof.host_phase("count_attempts", 0, 0, (uint64_t)attempt + 1); /* units: count tables tried (1 = the first was large enough) */
             DevBuf jt_buf, abnd_buf;
             Table jt{}, abnd{};
             unsigned long long cnt[4] = {0, 0, 0, 0};

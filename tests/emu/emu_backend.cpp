@@ -157,7 +157,7 @@ int index_from_stream(ReadStream& rs, int k, int abundance_min, int abundance_ma
     uint64_t cap = 1ull << 10;
     while (cap < std::max<size_t>(rs.size_hint(), 1 << 12) / 4) cap <<= 1;
     std::vector<uint64_t> histo(10003, 0);
-    for (;; cap <<= 1) {
+    for (uint64_t attempts = 1;; cap <<= 1, attempts++) {
         std::vector<uint64_t> keys(cap, ~0ULL);
         std::vector<uint32_t> cnts(cap, 0);
         CountTable t{keys.data(), cnts.data(), cap - 1};
@@ -183,6 +183,10 @@ int index_from_stream(ReadStream& rs, int k, int abundance_min, int abundance_ma
         if (int rc = index_from_kmers(km.data(), ct.data(), km.size(), k, out)) return rc;
         (*out)->info.abundance_min = abundance_min;
         (*out)->info.abundance_auto = autoc;
+        mtg_build_phase ph{};
+        snprintf(ph.name, sizeof ph.name, "count_attempts"); /* as the device build: units = count tables tried */
+        ph.units = attempts;
+        (*out)->build_phases.push_back(ph);
         return MTG_OK;
     }
 }
