@@ -118,6 +118,36 @@ int mtg_index_scan_sequences(const mtg_index* idx, const char* const* seqs, size
 int mtg_index_scan_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int mode,
                                  uint64_t* d_out_bits, mtg_scan_stats* st);
 
+/* Profile of sequences against the graph: per position membership, abundance and degrees, and the maximal runs of absent k-mers -- what the
+ * reference's `find` scan reads per reference position (src/FindBreakpoints.hpp:560-622,1012-1046), without its classification rules.
+ * One pass of the scan's tile structure (Bloom pre-filter in LDS, positives confirmed exactly); confirmed positions take their abundance and
+ * their neighbour masks from the look-ups of mtg_index_abundance / mtg_index_neighbors.  One word per position p of sequence s:
+ *   bits  0-7   abundance, saturating at 255 as mtg_index_abundance; 0 if absent
+ *   bits  8-11  successor mask of the k-mer as read along the sequence (bit order of mtg_index_neighbors)
+ *   bits 12-15  predecessor mask, same convention
+ *   bit  16     valid: all k characters are nucleotides (the character rule of mtg_index_scan_sequences)
+ *   bit  17     present: valid and in the graph (exact)
+ * Absent and invalid positions carry 0 in bits 0-15 (the reference stores nb_in = nb_out = 0 there, :1018-1027).
+ * A run is a maximal stretch of consecutive positions of one sequence that are valid and absent.  An invalid position is in no run: it ends
+ * one and does not count as a bound.  flags bit 0: position start - 1 exists and is present; bit 1: position start + length exists and is
+ * present.  Runs come in ascending (seq, start) order, extracted and ordered on the device.
+ * *n_runs is always the total number of runs; when it exceeds runs_cap the first runs_cap runs are written and the call still returns MTG_OK
+ * (the snprintf convention).  out[s] receives max(len(seqs[s]) - k + 1, 0) words; out may be NULL (runs and statistics only), runs may be
+ * NULL when runs_cap is 0, st may be NULL.  nseq = 0 and sequences shorter than k are legal. */
+#define MTG_PROFILE_ABUNDANCE(w) ((w) & 255u)
+#define MTG_PROFILE_SUCC(w) (((w) >> 8) & 15u)
+#define MTG_PROFILE_PRED(w) (((w) >> 12) & 15u)
+#define MTG_PROFILE_VALID(w) (((w) >> 16) & 1u)
+#define MTG_PROFILE_PRESENT(w) (((w) >> 17) & 1u)
+typedef struct mtg_run { uint32_t seq, start, length, flags; } mtg_run;
+typedef struct mtg_profile_stats { uint64_t n_positions, n_valid, n_present, n_runs, longest_run; double kernel_ms; } mtg_profile_stats;
+int mtg_index_profile_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, uint32_t* const* out, mtg_run* runs, size_t runs_cap, size_t* n_runs,
+                                mtg_profile_stats* st);
+/* same on 2-bit packed sequences already in DEVICE memory (layout of mtg_index_create_from_packed_device; no invalid positions): the word of
+ * position p of sequence s goes to d_out[d_pos_off[s] + p] (d_out and d_pos_off may be NULL), the runs to the device array d_runs */
+int mtg_index_profile_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, const uint64_t* d_pos_off,
+                                    uint32_t* d_out, mtg_run* d_runs, size_t runs_cap, size_t* n_runs, mtg_profile_stats* st);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Gap filling = Filler::gapFillFromSource over a batch of gaps.
  * ---------------------------------------------------------------------------------------------------------- */
@@ -390,6 +420,11 @@ int mtg_fill_main(int argc, const char* const* argv);
 /* The same behind Graph::load / Graph::create (src/Filler.cpp:172-226): the graph is an index that is already resident (options -in / -graph
  * are not expected; the index stays the caller's).  What a long-lived caller uses to run the tool's drivers and writers repeatedly. */
 int mtg_fill_main_on_index(mtg_index* idx, int argc, const char* const* argv);
+/* `MindTheGap profile (-in reads | -graph container) -ref genome.fa [-kmer-size -abundance-min -abundance-max] -out prefix`: the profile of a
+ * reference genome against the graph (not a module of the reference tool).  Writes prefix.absent.bed, one line per run of absent k-mers:
+ * name, start, start + length, length, L|R|LR|. (k-mer start positions, 0-based, half-open; name = the FASTA header up to the first blank),
+ * and prefix.profile.txt, the statistics as `key : value` lines.  Returns 0 / 1; nothing is written unless the whole profile succeeded. */
+int mtg_profile_main(int argc, const char* const* argv);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Tuning: every switch of the library -- capacities, A/B hooks of measured alternatives, hooks the tests use to force rare paths,

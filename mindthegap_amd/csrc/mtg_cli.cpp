@@ -1374,9 +1374,76 @@ static int run_tool(Options& O, mtg_index* idx, bool resident)
     return 0;
 }
 
+/* `MindTheGap profile`: the reference genome's k-mers against the graph (mtg_index_profile_sequences); the runs of absent k-mers as BED, the
+ * statistics as text.  Both files are written once the whole profile is there. */
+int profile_main(int argc, const char* const* argv)
+{
+    std::string in, graph, ref, out;
+    int k = 31, abundance_min = -1, abundance_max = 0;
+    for (int i = 0; i < argc; i++) {
+        const std::string a = argv[i];
+        auto val = [&](std::string& dst) -> bool { if (i + 1 >= argc) return false; dst = argv[++i]; return true; };
+        std::string v;
+        bool ok = true;
+        if (a == "-in") ok = val(in);
+        else if (a == "-graph") ok = val(graph);
+        else if (a == "-ref") ok = val(ref);
+        else if (a == "-out") ok = val(out);
+        else if (a == "-kmer-size") { ok = val(v); k = atoi(v.c_str()); }
+        else if (a == "-abundance-min") { ok = val(v); abundance_min = v == "auto" ? -1 : atoi(v.c_str()); }
+        else if (a == "-abundance-max") { ok = val(v); abundance_max = atoi(v.c_str()); }
+        else {
+            fprintf(stderr, "%sUsage: MindTheGap profile (-in <reads> | -graph <container>) -ref <genome.fa> [-kmer-size 31] [-abundance-min auto] [-abundance-max 0] -out <prefix>\n",
+                    (a == "-help" || a == "-h") ? "" : ("EXCEPTION: unknown option '" + a + "'\n").c_str());
+            return 1;
+        }
+        if (!ok) { fprintf(stderr, "EXCEPTION: missing value for option '%s'\n", a.c_str()); return 1; }
+    }
+    if (graph.empty() == in.empty()) { fprintf(stderr, "EXCEPTION: options -graph and -in are incompatible, but at least one of these is mandatory\n"); return 1; }
+    if (ref.empty() || out.empty()) { fprintf(stderr, "EXCEPTION: options -ref and -out are mandatory\n"); return 1; }
+    std::vector<std::pair<std::string, std::string>> recs;
+    if (!read_sequences(ref, recs)) { fprintf(stderr, "EXCEPTION: cannot read %s\n", ref.c_str()); return 1; }
+    mtg_index* idx = nullptr;
+    int rc = in.empty() ? index_load(graph.c_str(), &idx) : index_from_reads(in.c_str(), k, abundance_min, abundance_max, &idx);
+    if (rc) { fprintf(stderr, "EXCEPTION: %s\n", mtg_last_error()); return 1; }
+    std::vector<const char*> seqs(recs.size());
+    for (size_t i = 0; i < recs.size(); i++) seqs[i] = recs[i].second.c_str();
+    std::vector<mtg_run> runs(4096);
+    size_t n_runs = 0;
+    mtg_profile_stats st{};
+    rc = mtg_index_profile_sequences(idx, seqs.data(), seqs.size(), nullptr, runs.data(), runs.size(), &n_runs, &st);
+    if (!rc && n_runs > runs.size()) { /* the snprintf convention: once more with room for all of them */
+        runs.resize(n_runs);
+        rc = mtg_index_profile_sequences(idx, seqs.data(), seqs.size(), nullptr, runs.data(), runs.size(), &n_runs, &st);
+    }
+    const mtg_index_info info = idx->info;
+    mtg_index_free(idx);
+    if (rc || n_runs > runs.size()) { fprintf(stderr, "EXCEPTION: %s\n", rc ? mtg_last_error() : "the number of runs changed between two calls"); return 1; }
+    std::string bed, txt;
+    for (size_t i = 0; i < n_runs; i++) {
+        const mtg_run& r = runs[i];
+        const std::string& h = recs[r.seq].first;
+        bed.append(h, 0, h.find_first_of(" \t"));
+        appendf(bed, "\t%u\t%llu\t%u\t%s\n", r.start, (unsigned long long)r.start + r.length, r.length, r.flags == 3 ? "LR" : r.flags == 1 ? "L" : r.flags == 2 ? "R" : ".");
+    }
+    appendf(txt, "kmer_size : %d\nabundance_min : %d\nnb_solid_kmers : %llu\nnb_sequences : %zu\n", info.k, info.abundance_min, (unsigned long long)info.nb_solid_kmers, recs.size());
+    appendf(txt, "nb_positions : %llu\nnb_valid : %llu\nnb_present : %llu\nnb_absent : %llu\nnb_runs : %llu\nlongest_run : %llu\n", (unsigned long long)st.n_positions,
+            (unsigned long long)st.n_valid, (unsigned long long)st.n_present, (unsigned long long)(st.n_valid - st.n_present), (unsigned long long)st.n_runs,
+            (unsigned long long)st.longest_run);
+    const auto write_file = [](const std::string& name, const std::string& text) -> bool {
+        FILE* f = fopen(name.c_str(), "w");
+        if (!f) { fprintf(stderr, "EXCEPTION: Cannot open file %s for writing\n", name.c_str()); return false; }
+        const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+        return (fclose(f) == 0) && ok;
+    };
+    if (!write_file(out + ".absent.bed", bed) || !write_file(out + ".profile.txt", txt)) return 1;
+    return 0;
+}
+
 } // namespace mtgi
 
 extern "C" int mtg_fill_main(int argc, const char* const* argv) { return mtgi::fill_main(argc, argv); }
+extern "C" int mtg_profile_main(int argc, const char* const* argv) { return mtgi::profile_main(argc, argv); }
 extern "C" int mtg_fill_main_on_index(mtg_index* idx, int argc, const char* const* argv)
 {
     if (!idx) { mtgi::set_error("null argument"); return 1; }

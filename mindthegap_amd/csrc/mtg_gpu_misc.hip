@@ -3,12 +3,14 @@
  *
  *   k_query                          : batched contains / queryAbundance / successors / predecessors
  *   k_scan                           : rolling 2-bit k-mer + minimizer-blocked Bloom probe along packed sequences, blocks staged in LDS
+ *   k_profile, k_profile_*           : the scan's sibling that also answers abundance and degrees per position, and the runs of absent k-mers
  *   k_nw                             : Needleman-Wunsch match counts for the de-duplication of multi-path solutions, one wave per pair
  *                                      (remove_almost_identical_solutions, /root/reference/src/Utils.cpp:87-189,208-238)
  *   k_fmt_*                          : the tool's text (FASTA / info / VCF) of the sites with one solution (mtg_format.h)
  *   k_chase                          : dependent random 64-byte reads (measured roofline ceiling)
  */
 #include "mtg_gpu_common.h"
+#include "mtg_profile_runs.h"
 
 namespace mtgi {
 
@@ -292,6 +294,196 @@ __global__ void __launch_bounds__(SCAN_TILE) k_scan(Index ix, const uint64_t* __
     if (tid < 4 && s_tot[tid]) atomicAdd(&counters[tid], s_tot[tid]);
 }
 
+/* profile along packed sequences: k_scan's tile (the tile's m-mers hashed once in LDS, Bloom blocks staged by coalesced reads, pre-filter,
+ * exact confirmation), and for the confirmed positions the abundance and the neighbour masks of k_query, packed into one word per position
+ * (include/mtg_fill.h).  bad = one bit per NUCLEOTIDE that is no nucleotide (bit i % 64 of bad[word_off[s] + i / 64]; nullptr: none): a k-mer
+ * that covers one is invalid.  The valid and the present plane (bit layout of k_scan's output) go to vbits / pbits for k_profile_count /
+ * k_profile_write.  counters: [0] positions, [1] valid, [2] present */
+__global__ void __launch_bounds__(SCAN_TILE) k_profile(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off,
+                                                       const uint32_t* __restrict__ len, size_t nseq, const uint64_t* __restrict__ bad,
+                                                       const uint64_t* __restrict__ pos_off, uint32_t* out, uint64_t* vbits, uint64_t* pbits,
+                                                       unsigned long long* counters)
+{
+    __shared__ uint32_t s_blk[SCAN_TILE][16];
+    __shared__ uint64_t s_bid[SCAN_TILE];
+    __shared__ uint64_t s_slot_bid[SCAN_TILE];
+    __shared__ uint32_t s_wave_cnt[SCAN_TILE / 64];
+    __shared__ uint64_t s_mh[SCAN_TILE + 32]; /* hashes of the tile's m-mers */
+    const int k = ix.k, mm = ix.bloom.mm;
+    const uint32_t span = (uint32_t)(k - mm);
+    const uint64_t mk = kmask(k), mk1 = kmask(k - 1), mmask = kmask(mm);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    unsigned long long n_k = 0, n_valid = 0, n_present = 0;
+    for (size_t s = blockIdx.x; s < nseq; s += gridDim.x) {
+        const uint32_t L = len[s];
+        if (L < (uint32_t)k) continue;
+        const uint64_t* w = words + word_off[s];
+        const uint64_t* bw = bad ? bad + word_off[s] : nullptr;
+        uint64_t* vb = vbits + word_off[s];
+        uint64_t* pb = pbits + word_off[s];
+        uint32_t* ow = out ? out + pos_off[s] : nullptr;
+        const uint32_t npos = L - (uint32_t)k + 1;
+        for (uint32_t base = 0; base < npos; base += SCAN_TILE) {
+            const uint32_t p = base + tid;
+            const bool in_seq = p < npos;
+            const uint32_t tile_k = npos - base < (uint32_t)SCAN_TILE ? npos - base : (uint32_t)SCAN_TILE, tile_m = tile_k + span;
+            for (uint32_t t = tid; t < tile_m; t += SCAN_TILE) {
+                const uint32_t j = base + t, sh = 2u * (j & 31u);
+                uint64_t v = w[j >> 5] >> sh;
+                if ((j & 31u) + (uint32_t)mm > 32u) v |= w[(j >> 5) + 1] << (64u - sh);
+                s_mh[t] = bloom_mmer_hash(v & mmask, mm);
+            }
+            __syncthreads();
+            Kmer x;
+            x.f = x.r = 0;
+            uint64_t b = ~0ull;
+            bool ok = in_seq;
+            if (in_seq) {
+                x.r = le_kmer(w, p, mk) ^ (0xAAAAAAAAAAAAAAAAULL & mk);
+                x.f = revcomp(x.r, k);
+                uint64_t best = ~0ull;
+                for (uint32_t t = 0; t <= span; t++) { const uint64_t h = s_mh[tid + t]; best = h < best ? h : best; }
+                b = bloom_block_of_min(ix.bloom, best);
+                if (bw) { /* the k bits of the characters p .. p + k - 1 (k <= 32: at most two words) */
+                    const uint32_t sh = p & 63u;
+                    uint64_t m = bw[p >> 6] >> sh;
+                    if (sh + (uint32_t)k > 64u) m |= bw[(p >> 6) + 1] << (64u - sh);
+                    ok = (m & ((1ull << k) - 1ull)) == 0;
+                }
+            }
+            s_bid[tid] = b;
+            __syncthreads();
+            const bool leader = in_seq && (tid == 0 || s_bid[tid - 1] != b);
+            const unsigned long long bal = __ballot(leader);
+            const uint32_t prefix = (uint32_t)__popcll(bal & ((lane == 63u) ? ~0ull : ((2ull << lane) - 1ull)));
+            if (lane == 0) s_wave_cnt[wave] = (uint32_t)__popcll(bal);
+            __syncthreads();
+            uint32_t woff = 0, total = 0;
+            for (uint32_t i = 0; i < SCAN_TILE / 64; i++) { if (i < wave) woff += s_wave_cnt[i]; total += s_wave_cnt[i]; }
+            const uint32_t slot = woff + prefix - 1u; /* a follower at the start of a wave continues the last block of the previous wave */
+            if (leader) s_slot_bid[slot] = b;
+            __syncthreads();
+            for (uint32_t i = tid; i < total * 16u; i += SCAN_TILE) s_blk[i >> 4][i & 15u] = ix.bloom.bits[s_slot_bid[i >> 4] * 16u + (i & 15u)];
+            __syncthreads();
+            uint32_t word = 0;
+            if (in_seq) {
+                n_k++;
+                n_valid += ok;
+                if (ok) {
+                    word = 1u << 16;
+                    if (bloom_test_block(s_blk[slot], bloom_bits(canon(x)))) {
+                        uint32_t lines = 0;
+                        const uint32_t a = abundance(ix, x, lines);
+                        if (a) {
+                            const uint32_t succ = adj_right_t(ix.adj, x, mk1, lines).out, pred = adj_left(ix, x, mk1, lines).in;
+                            word |= (1u << 17) | (a > 255u ? 255u : a) | ((succ & 15u) << 8) | ((pred & 15u) << 12);
+                            n_present++;
+                        }
+                    }
+                }
+                if (ow) ow[p] = word;
+            }
+            const unsigned long long vbal = __ballot((word >> 16) & 1u), pbal = __ballot((word >> 17) & 1u);
+            if (lane == 0 && base + wave * 64u < npos) { vb[(base >> 6) + wave] = vbal; pb[(base >> 6) + wave] = pbal; }
+            __syncthreads();
+        }
+    }
+    __shared__ unsigned long long s_tot[3];
+    if (tid < 3) s_tot[tid] = 0;
+    __syncthreads();
+    atomicAdd(&s_tot[0], n_k); atomicAdd(&s_tot[1], n_valid); atomicAdd(&s_tot[2], n_present);
+    __syncthreads();
+    if (tid < 3 && s_tot[tid]) atomicAdd(&counters[tid], s_tot[tid]);
+}
+
+/* the runs of absent k-mers from the two planes (mtg_profile_runs.h), in ascending (seq, start) order by two counted passes:
+ * k_profile_count: runs that begin in each sequence; k_profile_seq_scan: their exclusive prefix sums (one workgroup), tot[0] = all runs;
+ * k_profile_write: every word numbers the runs that begin / end in it and writes its halves of their records; k_profile_finish: end ->
+ * length, tot[1] = the longest. */
+enum { RUNS_BLOCK = 256 };
+__device__ __forceinline__ uint32_t runs_block_sum(uint32_t v, uint32_t* s_w, uint32_t& excl)
+{
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    uint32_t x = v;
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)x, d, 64); if ((int)lane >= d) x += y; }
+    __syncthreads(); /* s_w of the previous call has been read */
+    if (lane == 63u) s_w[wv] = x;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (uint32_t i = 0; i < RUNS_BLOCK / 64; i++) { if (i < wv) before += s_w[i]; total += s_w[i]; }
+    excl = before + x - v;
+    return total;
+}
+__global__ void __launch_bounds__(RUNS_BLOCK) k_profile_count(const uint64_t* __restrict__ vbits, const uint64_t* __restrict__ pbits, const uint64_t* __restrict__ word_off,
+                                                              const uint32_t* __restrict__ len, size_t nseq, int k, uint32_t* seq_cnt)
+{
+    __shared__ uint32_t s_w[RUNS_BLOCK / 64];
+    for (size_t s = blockIdx.x; s < nseq; s += gridDim.x) {
+        const uint32_t L = len[s], npos = L < (uint32_t)k ? 0u : L - (uint32_t)k + 1u, nw = run_words(npos);
+        uint32_t mine = 0;
+        for (uint32_t w = threadIdx.x; w < nw; w += RUNS_BLOCK) mine += run_popc(run_word(vbits + word_off[s], pbits + word_off[s], w, npos).first);
+        uint32_t excl;
+        const uint32_t total = runs_block_sum(mine, s_w, excl);
+        if (threadIdx.x == 0) seq_cnt[s] = total;
+    }
+}
+__global__ void __launch_bounds__(1024) k_profile_seq_scan(const uint32_t* __restrict__ seq_cnt, size_t nseq, uint64_t* seq_before, unsigned long long* tot)
+{
+    __shared__ unsigned long long wsum[16];
+    __shared__ unsigned long long carry;
+    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
+    if (t == 0) carry = 0;
+    __syncthreads();
+    for (size_t b0 = 0; b0 < nseq; b0 += 1024) {
+        const size_t i = b0 + t;
+        const unsigned long long v = i < nseq ? seq_cnt[i] : 0;
+        unsigned long long x = v;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, d, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), d, 64);
+            if ((int)lane >= d) x += ((unsigned long long)hi << 32) | lo;
+        }
+        if (lane == 63) wsum[wv] = x;
+        __syncthreads();
+        unsigned long long before = carry;
+        for (uint32_t w2 = 0; w2 < wv; w2++) before += wsum[w2];
+        if (i < nseq) seq_before[i] = before + x - v;
+        __syncthreads();
+        if (t == 0) { unsigned long long c = carry; for (int w2 = 0; w2 < 16; w2++) c += wsum[w2]; carry = c; }
+        __syncthreads();
+    }
+    if (t == 0) tot[0] = carry;
+}
+__global__ void __launch_bounds__(RUNS_BLOCK) k_profile_write(const uint64_t* __restrict__ vbits, const uint64_t* __restrict__ pbits, const uint64_t* __restrict__ word_off,
+                                                              const uint32_t* __restrict__ len, size_t nseq, int k, const uint64_t* __restrict__ seq_before, mtg_run* runs,
+                                                              uint64_t cap)
+{
+    __shared__ uint32_t s_w[RUNS_BLOCK / 64];
+    for (size_t s = blockIdx.x; s < nseq; s += gridDim.x) {
+        const uint32_t L = len[s], npos = L < (uint32_t)k ? 0u : L - (uint32_t)k + 1u, nw = run_words(npos);
+        uint64_t before = seq_before[s];
+        if (before >= cap) continue; /* (uniform in the workgroup) */
+        for (uint32_t w0 = 0; w0 < nw; w0 += RUNS_BLOCK) {
+            const uint32_t w = w0 + threadIdx.x;
+            RunWord r;
+            r.first = r.last = r.lflag = r.rflag = 0; r.open = 0;
+            if (w < nw) r = run_word(vbits + word_off[s], pbits + word_off[s], w, npos);
+            uint32_t excl;
+            const uint32_t total = runs_block_sum(run_popc(r.first), s_w, excl);
+            if (w < nw) run_emit_word(r, (uint32_t)s, w, before + excl, runs, cap);
+            before += total;
+        }
+    }
+}
+__global__ void __launch_bounds__(RUNS_BLOCK) k_profile_finish(mtg_run* runs, uint64_t n, unsigned long long* tot)
+{
+    uint32_t longest = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * RUNS_BLOCK) {
+        const uint32_t l = run_finish(runs[i]);
+        longest = l > longest ? l : longest;
+    }
+    if (longest) atomicMax(&tot[1], (unsigned long long)longest);
+}
+
 /* dependent chains of random line reads: the access pattern of the simple-path walk.  LINE = bytes read per step (16..128) */
 template <int LINE>
 __global__ void __launch_bounds__(64) k_chase(const uint64_t* __restrict__ table, uint64_t nlines, uint64_t n_chains, uint32_t chain_len, uint64_t* sink)
@@ -546,6 +738,83 @@ int scan_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const u
     HIP_TRY(hipMemcpy(c, d_c.p, 32, hipMemcpyDeviceToHost));
     if (!device_ptrs) HIP_TRY(hipMemcpy(out_bits, pb, nwords * 8, hipMemcpyDeviceToHost));
     if (st) { st->n_kmers = c[0]; st->bloom_positive = c[1]; st->confirmed = c[2]; st->blocks_staged = c[3]; st->kernel_ms = ms; }
+    return MTG_OK;
+}
+
+/* profile over packed sequences (mtg_index_profile_sequences / _packed_device).  device_ptrs = 0: words / word_off / len / bad / pos_off are
+ * host arrays, out (npos_total words, or nullptr) and runs host memory; 1: all of them device memory (nwords, npos_total unused) */
+int profile_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad,
+                const uint64_t* pos_off, uint64_t npos_total, uint32_t* out, mtg_run* runs, size_t runs_cap, size_t* n_runs, int device_ptrs, mtg_profile_stats* st)
+{
+    if (int rc = use_device_of(idx)) return rc;
+    if (!idx || !idx->dev.bloom.bits) { set_error("the index has no Bloom filter (MTG_BLOOM_BITS=0)"); return MTG_ERR_ARG; }
+    *n_runs = 0;
+    if (st) *st = mtg_profile_stats{};
+    if (nseq == 0) return MTG_OK;
+    const int k = idx->dev.k;
+    DevBuf d_w, d_o, d_l, d_bad, d_po, d_out, d_v, d_p, d_cnt, d_before, d_c, d_runs;
+    const uint64_t *pw = words, *po = word_off, *pbad = bad, *ppo = pos_off;
+    const uint32_t* pl = len;
+    uint32_t* pout = out;
+    if (!device_ptrs) {
+        HIP_TRY(d_w.alloc(nwords * 8)); HIP_TRY(d_o.alloc(nseq * 8)); HIP_TRY(d_l.alloc(nseq * 4));
+        HIP_TRY(hipMemcpy(d_w.p, words, nwords * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_o.p, word_off, nseq * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_l.p, len, nseq * 4, hipMemcpyHostToDevice));
+        pw = d_w.as<uint64_t>(); po = d_o.as<uint64_t>(); pl = d_l.as<uint32_t>();
+        if (bad) { HIP_TRY(d_bad.alloc(nwords * 8)); HIP_TRY(hipMemcpy(d_bad.p, bad, nwords * 8, hipMemcpyHostToDevice)); pbad = d_bad.as<uint64_t>(); }
+        if (out) {
+            HIP_TRY(d_po.alloc(nseq * 8)); HIP_TRY(hipMemcpy(d_po.p, pos_off, nseq * 8, hipMemcpyHostToDevice));
+            HIP_TRY(d_out.alloc(npos_total * 4));
+            ppo = d_po.as<uint64_t>(); pout = d_out.as<uint32_t>();
+        }
+    } else { /* the planes take a word per 64 positions at the sequence's word offset: how far they reach */
+        std::vector<uint64_t> ho(nseq);
+        std::vector<uint32_t> hl(nseq);
+        HIP_TRY(hipMemcpy(ho.data(), word_off, nseq * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hl.data(), len, nseq * 4, hipMemcpyDeviceToHost));
+        nwords = 0;
+        for (size_t s = 0; s < nseq; s++) nwords = std::max<size_t>(nwords, (size_t)ho[s] + hl[s] / 64 + 1);
+    }
+    HIP_TRY(d_v.alloc(nwords * 8)); HIP_TRY(d_p.alloc(nwords * 8));
+    HIP_TRY(d_cnt.alloc(nseq * 4)); HIP_TRY(d_before.alloc(nseq * 8));
+    HIP_TRY(d_c.alloc(64));
+    HIP_TRY(hipMemset(d_c.p, 0, 64));
+    unsigned long long* cnt = d_c.as<unsigned long long>(); /* [0..2] k_profile's counters, [4] runs, [5] longest */
+    EventSet events;
+    hipEvent_t e0, e1, e2, e3;
+    HIP_TRY(events.make(e0)); HIP_TRY(events.make(e1)); HIP_TRY(events.make(e2)); HIP_TRY(events.make(e3));
+    const dim3 grid((unsigned)std::min<size_t>(nseq, 256 * 16));
+    HIP_TRY(hipEventRecord(e0, 0));
+    hipLaunchKernelGGL(k_profile, grid, dim3(SCAN_TILE), 0, 0, idx->dev, pw, po, pl, nseq, pbad, ppo, pout, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt);
+    hipLaunchKernelGGL(k_profile_count, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + 4);
+    HIP_TRY(hipEventRecord(e1, 0));
+    HIP_TRY(hipGetLastError());
+    unsigned long long c[8];
+    HIP_TRY(hipMemcpy(c, d_c.p, 64, hipMemcpyDeviceToHost));
+    const uint64_t total = c[4];
+    /* every run is written (the longest one may lie past runs_cap): into the caller's device array when it holds them all, else into one of our own */
+    mtg_run* pr = runs;
+    if (!device_ptrs || total > runs_cap) { HIP_TRY(d_runs.alloc((size_t)total * sizeof(mtg_run))); pr = d_runs.as<mtg_run>(); }
+    float ms0 = 0, ms1 = 0;
+    if (total) {
+        HIP_TRY(hipMemset(pr, 0, (size_t)total * sizeof(mtg_run)));
+        HIP_TRY(hipEventRecord(e2, 0));
+        hipLaunchKernelGGL(k_profile_write, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_before.as<uint64_t>(), pr, total);
+        hipLaunchKernelGGL(k_profile_finish, dim3((unsigned)std::min<uint64_t>((total + RUNS_BLOCK - 1) / RUNS_BLOCK, 256 * 16)), dim3(RUNS_BLOCK), 0, 0, pr, total, cnt + 4);
+        HIP_TRY(hipEventRecord(e3, 0));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventSynchronize(e3));
+        HIP_TRY(hipEventElapsedTime(&ms1, e2, e3));
+        HIP_TRY(hipMemcpy(c, d_c.p, 64, hipMemcpyDeviceToHost));
+        const size_t ncopy = (size_t)std::min<uint64_t>(total, runs_cap);
+        if (ncopy && pr != runs) HIP_TRY(hipMemcpy(runs, pr, ncopy * sizeof(mtg_run), device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(hipEventElapsedTime(&ms0, e0, e1));
+    if (!device_ptrs && out) HIP_TRY(hipMemcpy(out, pout, npos_total * 4, hipMemcpyDeviceToHost));
+    *n_runs = (size_t)total;
+    if (st) { st->n_positions = c[0]; st->n_valid = c[1]; st->n_present = c[2]; st->n_runs = total; st->longest_run = total ? c[5] : 0; st->kernel_ms = (double)ms0 + (double)ms1; }
     return MTG_OK;
 }
 

@@ -122,6 +122,15 @@ bool read_sequences(const std::string& path, std::vector<std::pair<std::string, 
     return clean;
 }
 
+/* The device side of the profile is mtg_gpu_misc.hip's.  The host code is also linked without that unit (the test harness that emulates the fill
+ * path on the CPU); there the profile does not exist, and says so. */
+__attribute__((weak)) int profile_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, const uint64_t*, uint64_t, uint32_t*,
+                                      mtg_run*, size_t, size_t*, int, mtg_profile_stats*)
+{
+    set_error("this build has no device code for the profile");
+    return MTG_ERR_NO_DEVICE;
+}
+
 /* ------------------------------------------------------------------------------------------------ index from reads */
 static inline bool nt_bad(unsigned char c) { return (c >> 3) & 1; } /* gatb: bit 3 of the ASCII code flags 'N' */
 
@@ -1848,6 +1857,46 @@ int mtg_index_scan_sequences(const mtg_index* idx, const char* const* seqs, size
         }
     }
     return MTG_OK;
+}
+
+int mtg_index_profile_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, uint32_t* const* out, mtg_run* runs, size_t runs_cap, size_t* n_runs,
+                                mtg_profile_stats* st)
+{
+    if (!idx || !n_runs || (nseq && !seqs) || (runs_cap && !runs)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    const int k = idx->dev.k;
+    std::vector<uint64_t> off(nseq), pos_off(nseq);
+    std::vector<uint32_t> len(nseq);
+    uint64_t nw = 0, npos = 0;
+    for (size_t s = 0; s < nseq; s++) {
+        if (!seqs[s] || (out && !out[s] && strlen(seqs[s]) >= (size_t)k)) { mtgi::set_error("sequence %zu: null pointer", s); return MTG_ERR_ARG; }
+        const size_t l = strlen(seqs[s]);
+        if (l > 0xFFFFFFFFull) { mtgi::set_error("sequence %zu: longer than 2^32 - 1", s); return MTG_ERR_ARG; }
+        len[s] = (uint32_t)l; off[s] = nw; nw += (len[s] + 31) / 32 + 2;
+        pos_off[s] = npos; npos += len[s] < (uint32_t)k ? 0 : len[s] - (uint32_t)k + 1;
+    }
+    /* the scan's packing, and next to it one bit per character that is no nucleotide: the device tells which k-mers cover one */
+    std::vector<uint64_t> words(nw + 2, 0), bad(nw + 2, 0);
+    for (size_t s = 0; s < nseq; s++)
+        for (uint32_t i = 0; i < len[s]; i++) {
+            const unsigned char ch = (unsigned char)seqs[s][i];
+            words[off[s] + (i >> 5)] |= (uint64_t)nt_code(ch) << (2 * (i & 31));
+            if (mtgi::nt_bad(ch)) bad[off[s] + (i >> 6)] |= 1ull << (i & 63);
+        }
+    std::vector<uint32_t> flat(out ? npos : 0);
+    int rc = mtgi::profile_run(idx, words.data(), words.size(), off.data(), len.data(), nseq, bad.data(), pos_off.data(), npos, out ? flat.data() : nullptr, runs, runs_cap, n_runs, 0, st);
+    if (rc) return rc;
+    if (out)
+        for (size_t s = 0; s < nseq; s++) {
+            const uint64_t n = (s + 1 < nseq ? pos_off[s + 1] : npos) - pos_off[s];
+            if (n) memcpy(out[s], flat.data() + pos_off[s], n * 4);
+        }
+    return MTG_OK;
+}
+int mtg_index_profile_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, const uint64_t* d_pos_off,
+                                    uint32_t* d_out, mtg_run* d_runs, size_t runs_cap, size_t* n_runs, mtg_profile_stats* st)
+{
+    if (!idx || !n_runs || (nseq && (!d_words || !d_word_off || !d_len)) || (d_out && !d_pos_off) || (runs_cap && !d_runs)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    return mtgi::profile_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, d_pos_off, 0, d_out, d_runs, runs_cap, n_runs, 1, st);
 }
 
 int mtg_nw_matches(const char* const* a, const char* const* b, size_t n, uint32_t* matches)

@@ -585,6 +585,11 @@ void batch_release_device(FillInput& in);
 /* membership scan over packed sequences: host arrays in (words/off/len), bit output as in mtg_index_scan_packed_device; device = 1: the pointers are device pointers */
 int scan_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, int mode, uint64_t* out_bits, int device_ptrs,
              mtg_scan_stats* st);
+/* profile over packed sequences (mtg_gpu_misc.hip): device_ptrs = 0: host arrays in (bad = one bit per character that is no nucleotide, at the sequence's
+ * word offset; may be null), out = npos_total words in the order of pos_off (may be null), runs = host array; 1: everything is device memory */
+int profile_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad,
+                const uint64_t* pos_off, uint64_t npos_total, uint32_t* out, mtg_run* runs, size_t runs_cap, size_t* n_runs, int device_ptrs, mtg_profile_stats* st);
+int profile_main(int argc, const char* const* argv);
 
 /* The reads of Graph::create as a stream of text blocks: whole sequences separated by '\n' (an invalid character by gatb's rule, so no k-mer
  * spans two reads), at most a few hundred MB each; rewind() starts over (the counting may need several passes over the reads). */

@@ -1,6 +1,7 @@
 /*
  * mtg_main.cpp -- the `MindTheGap` executable: module dispatch of /root/reference/src/main.cpp:62-124.
- * Only the `fill` module is in scope; `find` is the reference's other module.
+ * Only the `fill` module is in scope; `find` is the reference's other module.  `profile` is this build's own: the data access
+ * underneath `find` (a reference genome's k-mers against the graph), without its classification.
  */
 #include "../../include/mtg_fill.h"
 #include <cstdio>
@@ -14,6 +15,7 @@ int main(int argc, char** argv)
     }
     if (strcmp(argv[1], "-version") == 0 || strcmp(argv[1], "-v") == 0) { printf("MindTheGap version 2.3.0 (mindthegap_amd, HIP gfx950)\n"); return 0; }
     if (strcmp(argv[1], "fill") == 0) return mtg_fill_main(argc - 2, (const char* const*)(argv + 2));
+    if (strcmp(argv[1], "profile") == 0) return mtg_profile_main(argc - 2, (const char* const*)(argv + 2));
     if (strcmp(argv[1], "find") == 0) { fprintf(stderr, "EXCEPTION: the find module is not part of this build; use the reference MindTheGap find and pass its .breakpoints to fill\n"); return 1; }
     fprintf(stderr, "EXCEPTION: unknown module '%s'\n", argv[1]);
     return 1;

@@ -93,6 +93,35 @@ class ScanStats(C.Structure):
     _fields_ = [("n_kmers", C.c_uint64), ("bloom_positive", C.c_uint64), ("confirmed", C.c_uint64), ("blocks_staged", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
+class ProfileStats(C.Structure):
+    _fields_ = [("n_positions", C.c_uint64), ("n_valid", C.c_uint64), ("n_present", C.c_uint64), ("n_runs", C.c_uint64), ("longest_run", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+# a run of absent k-mers (mtg_run): flags bit 0 / bit 1 = a present position right before / right behind it
+RUN_DTYPE = np.dtype([("seq", np.uint32), ("start", np.uint32), ("length", np.uint32), ("flags", np.uint32)])
+
+
+# the word of a position in a profile (include/mtg_fill.h); each takes a word or an array of words
+def profile_abundance(w):
+    return w & 255
+
+
+def profile_succ(w):
+    return (w >> 8) & 15
+
+
+def profile_pred(w):
+    return (w >> 12) & 15
+
+
+def profile_valid(w):
+    return (w >> 16) & 1
+
+
+def profile_present(w):
+    return (w >> 17) & 1
+
+
 class BatchStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("post_kernel_ms", C.c_double), ("total_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double), ("host_ms", C.c_double), ("marshal_ms", C.c_double), ("result_ms", C.c_double),
                 ("index_lines", C.c_uint64), ("n_launches", C.c_uint64), ("n_retried_gaps", C.c_uint64), ("contig_nt", C.c_uint64),
@@ -164,6 +193,10 @@ def _bind(lib):
     lib.mtg_index_neighbors.argtypes = [C.c_void_p, P(C.c_uint64), C.c_size_t, P(C.c_uint8), P(C.c_uint8)]
     lib.mtg_index_scan_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, C.c_int, P(P(C.c_uint8)), P(ScanStats)]
     lib.mtg_index_scan_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, P(ScanStats)]
+    lib.mtg_index_profile_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, P(P(C.c_uint32)), C.c_void_p, C.c_size_t, P(C.c_size_t), P(ProfileStats)]
+    lib.mtg_index_profile_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, P(C.c_size_t),
+                                                    P(ProfileStats)]
+    lib.mtg_profile_main.argtypes = [C.c_int, P(C.c_char_p)]
     lib.mtg_default_params.argtypes = [P(Params)]
     lib.mtg_default_params.restype = None
     lib.mtg_fill_batch.argtypes = [C.c_void_p, P(Params), P(CGap), C.c_size_t, P(C.c_void_p)]
@@ -456,6 +489,34 @@ class Index:
         _check(self.lib.mtg_index_scan_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, 1 if exact else 0, out_bits_ptr, C.byref(st)))
         return {f[0]: getattr(st, f[0]) for f in ScanStats._fields_}
 
+    def profile_sequences(self, seqs, want_positions=True, runs_cap=None):
+        """membership, abundance and degrees of the k-mer at every position (one uint32 word each, see profile_abundance / _succ / _pred / _valid /
+        _present) and the maximal runs of valid, absent positions; returns (list of uint32 arrays or None, runs as a RUN_DTYPE array in (seq, start)
+        order, stats dict).  runs_cap: give the run array that capacity and return the leading runs (stats["n_runs"] is always the total); by
+        default the array is sized to hold them all, with a second call when the first capacity was too small."""
+        k = self.info()["k"]
+        n = len(seqs)
+        arr = (C.c_char_p * n)(*[s.encode() for s in seqs])
+        outs = ptrs = None
+        if want_positions:
+            outs = [np.zeros(max(len(s) - k + 1, 0), dtype=np.uint32) for s in seqs]
+            ptrs = (C.POINTER(C.c_uint32) * n)(*[o.ctypes.data_as(C.POINTER(C.c_uint32)) for o in outs])
+        cap = 1024 if runs_cap is None else int(runs_cap)
+        while True:
+            runs = np.zeros(cap, dtype=RUN_DTYPE)
+            total, st = C.c_size_t(), ProfileStats()
+            _check(self.lib.mtg_index_profile_sequences(self.h, arr, n, ptrs, runs.ctypes.data if cap else None, cap, C.byref(total), C.byref(st)))
+            if runs_cap is not None or total.value <= cap:
+                break
+            cap = total.value
+        return outs, runs[:min(total.value, cap)], {f[0]: getattr(st, f[0]) for f in ProfileStats._fields_}
+
+    def profile_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, pos_off_ptr, out_ptr, runs_ptr, runs_cap):
+        """the same on packed sequences in device memory (pointers as integers; out_ptr / pos_off_ptr may be None); returns (total runs, stats dict)"""
+        total, st = C.c_size_t(), ProfileStats()
+        _check(self.lib.mtg_index_profile_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, pos_off_ptr, out_ptr, runs_ptr, runs_cap, C.byref(total), C.byref(st)))
+        return total.value, {f[0]: getattr(st, f[0]) for f in ProfileStats._fields_}
+
     def stage_a(self, sources, targets, params=None):
         """Contigs of every gap (gatb IterativeExtensions::construct_linear_seqs, src/Filler.cpp:884)."""
         params = params or FillParams()
@@ -740,6 +801,12 @@ def fill_main(argv):
     """`MindTheGap fill <argv>` (Filler::run, src/main.cpp:105-120); returns the exit code."""
     arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
     return load_library().mtg_fill_main(len(argv), arr)
+
+
+def profile_main(argv):
+    """`MindTheGap profile <argv>`: writes <out>.absent.bed and <out>.profile.txt; returns the exit code."""
+    arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
+    return load_library().mtg_profile_main(len(argv), arr)
 
 
 def nw_matches(pairs):
