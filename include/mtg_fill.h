@@ -148,6 +148,32 @@ int mtg_index_profile_sequences(const mtg_index* idx, const char* const* seqs, s
 int mtg_index_profile_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, const uint64_t* d_pos_off,
                                     uint32_t* d_out, mtg_run* d_runs, size_t runs_cap, size_t* n_runs, mtg_profile_stats* st);
 
+/* `find` for homozygous insertions: the gaps of the reference's scan (src/FindBreakpoints.hpp:560-622 -- not the profile's runs: a single
+ * present position does not end a gap, see csrc/mtg_find_gaps.h) judged by its gap observers FindSmallCleanInsertion, FindSmallFuzzyInsertion
+ * (src/FindSmallInsertion.hpp), FindCleanInsertion and FindFuzzyInsertion (src/FindInsertion.hpp), in that order; no other observer runs.
+ * A gap of L positions whose first solid position behind it is e has the repeat r = k - 1 - L; with 0 <= r <= max_repeat and a valid k-mer
+ * right before it, it is an insertion of 1-2 nt when one of the 20 strings A, C, G, T, AA .. TT between the left k-mer and the k
+ * nucleotides at e + r spells k solid windows (the first such string), else an insertion site.  One record per call:
+ *   pos    0-based, as the observers pass it to writeBreakpoint / writeIndel: e - 1 for an insertion, e - 1 + r for a site
+ *   kind   0 insertion site, 1 insertion of 1-2 nt
+ *   repeat r (the FUZZY / fuzzy_ field)
+ *   left, right   positions in the sequence of the two k-mers as written (right = e + r)
+ *   ins    index 0..19 of the inserted string in that order; 0 for sites
+ * Records come in the order of the scan (ascending seq, then e), ordered on the device.  max_repeat < 0 is refused; values above k - 2 act as k - 2.
+ * *n_calls is always the total; when it exceeds cap the first cap records are written and the call still returns MTG_OK.  calls may be NULL
+ * when cap is 0, st may be NULL.  The character rule is that of mtg_index_profile_sequences. */
+typedef struct mtg_find_call { uint32_t seq, pos, kind, repeat, left, right, ins; } mtg_find_call;
+typedef struct mtg_find_stats {
+    uint64_t n_positions, n_gaps /* calls of the gap observers */, n_candidates /* of those, r in range and the left k-mer valid */;
+    uint64_t n_homo_clean, n_homo_fuzzy /* sites */, n_small_clean, n_small_fuzzy /* insertions of 1-2 nt, r = 0 / r > 0 */;
+    double kernel_ms;
+} mtg_find_stats;
+int mtg_index_find_homo_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls,
+                                  mtg_find_stats* st);
+/* same on 2-bit packed sequences already in DEVICE memory (layout of mtg_index_profile_packed_device; no invalid positions); d_calls is a device array */
+int mtg_index_find_homo_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
+                                      mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_stats* st);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Gap filling = Filler::gapFillFromSource over a batch of gaps.
  * ---------------------------------------------------------------------------------------------------------- */
@@ -425,6 +451,14 @@ int mtg_fill_main_on_index(mtg_index* idx, int argc, const char* const* argv);
  * name, start, start + length, length, L|R|LR|. (k-mer start positions, 0-based, half-open; name = the FASTA header up to the first blank),
  * and prefix.profile.txt, the statistics as `key : value` lines.  Returns 0 / 1; nothing is written unless the whole profile succeeded. */
 int mtg_profile_main(int argc, const char* const* argv);
+/* `MindTheGap find (-in reads | -graph container) -ref genome.fa -homo-insertions [-max-rep 5] [-kmer-size -abundance-min -abundance-max]
+ * [-out prefix]`: the part of the reference's `find` that mtg_index_find_homo_sequences covers.  Without -homo-insertions it stops with a
+ * message that names what is not built (SNPs, deletions, heterozygous sites, -bed) and returns 1.  Writes prefix.breakpoints (writeBreakpoint,
+ * src/FindBreakpoints.hpp:640-658) and prefix.othervariants.vcf (header of src/Finder.cpp:513-541, records of writeIndel); ids bkptN count
+ * from 1 in detection order across both files; the REPEATED field stays empty (the reference fills it from a Bloom filter of the genome's
+ * (k-1)-mers, whose false positives are not reproducible).  Prints the Results block of the reference's summary.  Returns 0 / 1; nothing is
+ * written unless the whole scan succeeded. */
+int mtg_find_main(int argc, const char* const* argv);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Tuning: every switch of the library -- capacities, A/B hooks of measured alternatives, hooks the tests use to force rare paths,

@@ -1440,10 +1440,116 @@ int profile_main(int argc, const char* const* argv)
     return 0;
 }
 
+/* `MindTheGap find -homo-insertions`: the homozygous insertion sites and the insertions of 1-2 nt of a reference genome against the graph
+ * (mtg_index_find_homo_sequences), in the reference's two files.  Both are written once the whole scan is there. */
+int find_main(int argc, const char* const* argv)
+{
+    std::string in, graph, ref, out = "MindTheGap_Expe"; /* the reference names it after the date (src/Finder.cpp: MindTheGap_Expe-<date>) */
+    int k = 31, abundance_min = -1, abundance_max = 0, max_repeat = 5;
+    bool homo_only = false;
+    const char* usage = "Usage: MindTheGap find (-in <reads> | -graph <container>) -ref <genome.fa> -homo-insertions [-max-rep 5] [-kmer-size 31] [-abundance-min auto] [-abundance-max 0] [-out <prefix>]\n";
+    for (int i = 0; i < argc; i++) {
+        const std::string a = argv[i];
+        auto val = [&](std::string& dst) -> bool { if (i + 1 >= argc) return false; dst = argv[++i]; return true; };
+        std::string v;
+        bool ok = true;
+        if (a == "-in") ok = val(in);
+        else if (a == "-graph") ok = val(graph);
+        else if (a == "-ref") ok = val(ref);
+        else if (a == "-out") ok = val(out);
+        else if (a == "-homo-insertions") homo_only = true;
+        else if (a == "-max-rep") { ok = val(v); max_repeat = atoi(v.c_str()); }
+        else if (a == "-kmer-size") { ok = val(v); k = atoi(v.c_str()); }
+        else if (a == "-abundance-min") { ok = val(v); abundance_min = v == "auto" ? -1 : atoi(v.c_str()); }
+        else if (a == "-abundance-max") { ok = val(v); abundance_max = atoi(v.c_str()); }
+        else {
+            fprintf(stderr, "%s%s", (a == "-help" || a == "-h") ? "" : ("EXCEPTION: unknown option '" + a + "'\n").c_str(), usage);
+            return 1;
+        }
+        if (!ok) { fprintf(stderr, "EXCEPTION: missing value for option '%s'\n", a.c_str()); return 1; }
+    }
+    if (!homo_only) {
+        fprintf(stderr, "EXCEPTION: this build of find detects homozygous insertions only (sites and insertions of 1-2 nt): SNPs, deletions, heterozygous sites and -bed are "
+                        "not built.  Pass -homo-insertions to run that subset; its output is not the reference's default find.\n%s", usage);
+        return 1;
+    }
+    if (graph.empty() == in.empty()) { fprintf(stderr, "EXCEPTION: options -graph and -in are incompatible, but at least one of these is mandatory\n"); return 1; }
+    if (ref.empty()) { fprintf(stderr, "EXCEPTION: option -ref is mandatory\n"); return 1; }
+    if (max_repeat < 0) { fprintf(stderr, "EXCEPTION: -max-rep must not be negative\n"); return 1; }
+    std::vector<std::pair<std::string, std::string>> recs;
+    if (!read_sequences(ref, recs)) { fprintf(stderr, "EXCEPTION: cannot read %s\n", ref.c_str()); return 1; }
+    mtg_index* idx = nullptr;
+    int rc = in.empty() ? index_load(graph.c_str(), &idx) : index_from_reads(in.c_str(), k, abundance_min, abundance_max, &idx);
+    if (rc) { fprintf(stderr, "EXCEPTION: %s\n", mtg_last_error()); return 1; }
+    std::vector<const char*> seqs(recs.size());
+    for (size_t i = 0; i < recs.size(); i++) seqs[i] = recs[i].second.c_str();
+    std::vector<mtg_find_call> calls(4096);
+    size_t n_calls = 0;
+    mtg_find_stats st{};
+    const time_t t_start = time(0);
+    rc = mtg_index_find_homo_sequences(idx, seqs.data(), seqs.size(), max_repeat, calls.data(), calls.size(), &n_calls, &st);
+    if (!rc && n_calls > calls.size()) { /* the snprintf convention: once more with room for all of them */
+        calls.resize(n_calls);
+        rc = mtg_index_find_homo_sequences(idx, seqs.data(), seqs.size(), max_repeat, calls.data(), calls.size(), &n_calls, &st);
+    }
+    const double seconds = difftime(time(0), t_start);
+    const mtg_index_info info = idx->info;
+    mtg_index_free(idx);
+    if (rc || n_calls > calls.size()) { fprintf(stderr, "EXCEPTION: %s\n", rc ? mtg_last_error() : "the number of calls changed between two calls"); return 1; }
+    k = info.k;
+    std::string bkpt, vcf;
+    {   /* Finder::writeVcfHeader, src/Finder.cpp:513-541 */
+        const time_t now = time(nullptr);
+        appendf(vcf, "##fileformat=VCFv4.1\n##filedate=%s##source=MindTheGap find version %s\n##SAMPLE=file:%s\n##REF=file:%s\n", ctime(&now), MTG_VERSION, in.empty() ? graph.c_str() : in.c_str(), ref.c_str());
+        vcf += "##INFO=<ID=TYPE,Number=1,Type=String,Description=\"SNP, INS, DEL or .\">\n##INFO=<ID=LEN,Number=1,Type=Integer,Description=\"variant size\">\n"
+               "##INFO=<ID=FUZZY,Number=1,Type=Integer,Description=\"repeat size at the breakpoint, only for INS and DEL\">\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+               "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tG1\n";
+    }
+    static const char* const nucleo[20] = {"A", "C", "G", "T", "AA", "AC", "AG", "AT", "CA", "CC", "CG", "CT", "GA", "GC", "GG", "GT", "TA", "TC", "TG", "TT"};
+    const auto kmer_string = [&](const std::string& s, uint32_t p) { /* model().toString of the k-mer at p: upper case */
+        std::string o((size_t)k, 'A');
+        for (int i = 0; i < k; i++) o[(size_t)i] = "ACTG"[((unsigned char)s[p + (uint32_t)i] >> 1) & 3];
+        return o;
+    };
+    for (size_t i = 0; i < n_calls; i++) {
+        const mtg_find_call& c = calls[i];
+        const std::string& h = recs[c.seq].first;
+        const std::string name = h.substr(0, h.find_first_of(" \t")), &s = recs[c.seq].second;
+        const std::string left = kmer_string(s, c.left);
+        const int id = (int)i + 1;
+        if (c.kind == 0) { /* writeBreakpoint, src/FindBreakpoints.hpp:640-658; the fuzzy right k-mer is the genome's text as it stands (FindInsertion.hpp:114) */
+            const std::string right = c.repeat ? s.substr(c.right, (size_t)k) : kmer_string(s, c.right);
+            appendf(bkpt, ">bkpt%i_%s_pos_%lli_fuzzy_%i_HOM %s left_kmer\n%s\n>bkpt%i_%s_pos_%lli_fuzzy_%i_HOM %s right_kmer\n%s\n", id, name.c_str(), (long long)c.pos + 1, (int)c.repeat, "",
+                    left.c_str(), id, name.c_str(), (long long)c.pos + 1, (int)c.repeat, "", right.c_str());
+        } else { /* writeIndel, :679-702 */
+            const std::string r(1, left[(size_t)(k - 1) - c.repeat]), alt = r + nucleo[c.ins < 20 ? c.ins : 0];
+            appendf(vcf, "%s\t%lli\tbkpt%i\t%s\t%s\t.\tPASS\tTYPE=INS;LEN=%i;FUZZY=%i\tGT\t1/1\n", name.c_str(), (long long)c.pos + 1, id, r.c_str(), alt.c_str(), (int)alt.size() - 1, (int)c.repeat);
+        }
+    }
+    const auto write_file = [](const std::string& name, const std::string& text) -> bool {
+        FILE* f = fopen(name.c_str(), "w");
+        if (!f) { fprintf(stderr, "EXCEPTION: Cannot open file %s for writing\n", name.c_str()); return false; }
+        const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+        return (fclose(f) == 0) && ok;
+    };
+    if (!write_file(out + ".breakpoints", bkpt) || !write_file(out + ".othervariants.vcf", vcf)) return 1;
+    /* resumeResults, src/Finder.cpp:483-511: the counters this build has */
+    printf("MindTheGap find\n    version                                  : %s\n    backend                                  : mindthegap_amd (HIP, gfx950)\n", MTG_VERSION);
+    printf("    Breakpoint detection options\n        max_repeat                               : %i\n        homo_insertions                          : yes\n"
+           "        hete_insertions                          : no\n        snp                                      : no\n        deletion                                 : no\n", max_repeat);
+    printf("Results\n    Insertion breakpoints\n        homozygous                               : %llu\n            clean                                    : %llu\n"
+           "            fuzzy                                    : %llu\n", (unsigned long long)(st.n_homo_clean + st.n_homo_fuzzy), (unsigned long long)st.n_homo_clean, (unsigned long long)st.n_homo_fuzzy);
+    printf("    Other variants\n        Homozygous insertions 1-2 bp size        : %llu\n", (unsigned long long)(st.n_small_clean + st.n_small_fuzzy));
+    printf("    Time                                     : %.1f s\n    Output files\n        breakpoint_file                          : %s.breakpoints\n        othervariants_file                       : %s.othervariants.vcf\n",
+           seconds, out.c_str(), out.c_str());
+    return 0;
+}
+
 } // namespace mtgi
 
 extern "C" int mtg_fill_main(int argc, const char* const* argv) { return mtgi::fill_main(argc, argv); }
 extern "C" int mtg_profile_main(int argc, const char* const* argv) { return mtgi::profile_main(argc, argv); }
+extern "C" int mtg_find_main(int argc, const char* const* argv) { return mtgi::find_main(argc, argv); }
 extern "C" int mtg_fill_main_on_index(mtg_index* idx, int argc, const char* const* argv)
 {
     if (!idx) { mtgi::set_error("null argument"); return 1; }

@@ -4,6 +4,8 @@
  *   k_query                          : batched contains / queryAbundance / successors / predecessors
  *   k_scan                           : rolling 2-bit k-mer + minimizer-blocked Bloom probe along packed sequences, blocks staged in LDS
  *   k_profile, k_profile_*           : the scan's sibling that also answers abundance and degrees per position, and the runs of absent k-mers
+ *   k_find_*, k_mark_*               : `find` for homozygous insertions: the scan's gaps, their candidates compacted in order, one wave per
+ *                                      candidate for the degree tests and the micro-assembly of 1-2 nt, the calls compacted in order
  *   k_nw                             : Needleman-Wunsch match counts for the de-duplication of multi-path solutions, one wave per pair
  *                                      (remove_almost_identical_solutions, /root/reference/src/Utils.cpp:87-189,208-238)
  *   k_fmt_*                          : the tool's text (FASTA / info / VCF) of the sites with one solution (mtg_format.h)
@@ -11,6 +13,7 @@
  */
 #include "mtg_gpu_common.h"
 #include "mtg_profile_runs.h"
+#include "mtg_find_gaps.h"
 
 namespace mtgi {
 
@@ -414,6 +417,12 @@ __device__ __forceinline__ uint32_t runs_block_sum(uint32_t v, uint32_t* s_w, ui
     excl = before + x - v;
     return total;
 }
+/* GAPS = false: the profile's runs (run_word); true: the gaps of the `find` scan (gap_word, mtg_find_gaps.h) -- the predicate is the only difference */
+template <bool GAPS> MTG_DEV RunWord runs_or_gaps_word(const uint64_t* vplane, const uint64_t* pplane, uint32_t w, uint32_t npos)
+{
+    return GAPS ? gap_word(vplane, pplane, w, npos) : run_word(vplane, pplane, w, npos);
+}
+template <bool GAPS>
 __global__ void __launch_bounds__(RUNS_BLOCK) k_profile_count(const uint64_t* __restrict__ vbits, const uint64_t* __restrict__ pbits, const uint64_t* __restrict__ word_off,
                                                               const uint32_t* __restrict__ len, size_t nseq, int k, uint32_t* seq_cnt)
 {
@@ -421,7 +430,7 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_profile_count(const uint64_t* __
     for (size_t s = blockIdx.x; s < nseq; s += gridDim.x) {
         const uint32_t L = len[s], npos = L < (uint32_t)k ? 0u : L - (uint32_t)k + 1u, nw = run_words(npos);
         uint32_t mine = 0;
-        for (uint32_t w = threadIdx.x; w < nw; w += RUNS_BLOCK) mine += run_popc(run_word(vbits + word_off[s], pbits + word_off[s], w, npos).first);
+        for (uint32_t w = threadIdx.x; w < nw; w += RUNS_BLOCK) mine += run_popc(runs_or_gaps_word<GAPS>(vbits + word_off[s], pbits + word_off[s], w, npos).first);
         uint32_t excl;
         const uint32_t total = runs_block_sum(mine, s_w, excl);
         if (threadIdx.x == 0) seq_cnt[s] = total;
@@ -453,6 +462,7 @@ __global__ void __launch_bounds__(1024) k_profile_seq_scan(const uint32_t* __res
     }
     if (t == 0) tot[0] = carry;
 }
+template <bool GAPS>
 __global__ void __launch_bounds__(RUNS_BLOCK) k_profile_write(const uint64_t* __restrict__ vbits, const uint64_t* __restrict__ pbits, const uint64_t* __restrict__ word_off,
                                                               const uint32_t* __restrict__ len, size_t nseq, int k, const uint64_t* __restrict__ seq_before, mtg_run* runs,
                                                               uint64_t cap)
@@ -466,7 +476,7 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_profile_write(const uint64_t* __
             const uint32_t w = w0 + threadIdx.x;
             RunWord r;
             r.first = r.last = r.lflag = r.rflag = 0; r.open = 0;
-            if (w < nw) r = run_word(vbits + word_off[s], pbits + word_off[s], w, npos);
+            if (w < nw) r = runs_or_gaps_word<GAPS>(vbits + word_off[s], pbits + word_off[s], w, npos);
             uint32_t excl;
             const uint32_t total = runs_block_sum(run_popc(r.first), s_w, excl);
             if (w < nw) run_emit_word(r, (uint32_t)s, w, before + excl, runs, cap);
@@ -482,6 +492,129 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_profile_finish(mtg_run* runs, ui
         longest = l > longest ? l : longest;
     }
     if (longest) atomicMax(&tot[1], (unsigned long long)longest);
+}
+
+/* ---- `find` for homozygous insertions (include/mtg_fill.h: mtg_index_find_homo_sequences).  The gaps of the scan come from
+ * k_profile_count<true> / k_profile_write<true> as mtg_run records (flags: mtg_find_gaps.h).
+ * k_find_mark: one thread per gap, the length test alone -- mark[i] = the gap is a candidate; counters[0] += gaps the observers see.
+ * k_mark_count / k_profile_seq_scan / k_mark_index: the indices of the non-zero marks in ascending order (counts per workgroup, their
+ * exclusive prefix sums, then every workgroup numbers its own); used for the candidates and, after k_find_assemble, for the calls. */
+__global__ void __launch_bounds__(RUNS_BLOCK) k_find_mark(const mtg_run* __restrict__ gaps, uint64_t n, int k, int max_repeat, uint32_t* mark, unsigned long long* counters)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    bool seen = false;
+    if (i < n) {
+        const mtg_run g = gaps[i];
+        seen = (g.flags & 2u) != 0;
+        mark[i] = gap_is_candidate(g.length, g.flags, k, max_repeat) ? 1u : 0u;
+    }
+    const unsigned long long bal = __ballot(seen);
+    if ((threadIdx.x & 63u) == 0 && bal) atomicAdd(&counters[0], (unsigned long long)__popcll(bal));
+}
+__global__ void __launch_bounds__(RUNS_BLOCK) k_mark_count(const uint32_t* __restrict__ mark, uint64_t n, uint32_t* blk_cnt)
+{
+    __shared__ uint32_t s_w[RUNS_BLOCK / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    uint32_t excl;
+    const uint32_t total = runs_block_sum((i < n && mark[i]) ? 1u : 0u, s_w, excl);
+    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = total;
+}
+__global__ void __launch_bounds__(RUNS_BLOCK) k_mark_index(const uint32_t* __restrict__ mark, uint64_t n, const uint64_t* __restrict__ blk_before, uint32_t* index, uint64_t cap)
+{
+    __shared__ uint32_t s_w[RUNS_BLOCK / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    const bool on = i < n && mark[i];
+    uint32_t excl;
+    runs_block_sum(on ? 1u : 0u, s_w, excl);
+    const uint64_t at = blk_before[blockIdx.x] + excl;
+    if (on && at < cap) index[at] = (uint32_t)i;
+}
+
+/* The observers on one candidate gap, one wave each (four to a workgroup).  Gap of L positions from `start`, first solid position behind it
+ * e = start + L, r = k - 1 - L: left k-mer at start - 1 (present: an anchor), right k-mer as written at e + r, which for r > 0 must lie in
+ * the sequence and hold nucleotides only.  Lane 0 / lane 1 look up outdegree(left) / indegree(k-mer at e); every observer but the small
+ * clean one wants both >= 1 (FindSmallInsertion.hpp:64 has no such test: kept).  The micro-assembly takes two of the 20 strings at a time:
+ * lanes 0-31 the windows 0 .. k-1 of left + ins + right for string 2 * it, lanes 32-63 those of string 2 * it + 1 (k <= 32); a window is cut
+ * from the 128-bit little-endian image of the text and looked up by the path of k_query (abundance != 0).  A string is called when its first
+ * k windows are all solid -- the windows behind them are not looked at, as in the reference, where nothing depends on them any more -- and
+ * the first string in the order A, C, G, T, AA .. TT wins: the loop leaves at the first pair with a hit, the lower half before the upper.
+ * res[c] = 0: no call; else 1 | kind << 1 | ins << 8.  counters[2..5] += homo clean, homo fuzzy, small clean, small fuzzy */
+enum { FIND_WAVES = 4 };
+__global__ void __launch_bounds__(FIND_WAVES * 64) k_find_assemble(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off, const uint32_t* __restrict__ len,
+                                                                   const uint64_t* __restrict__ bad, const mtg_run* __restrict__ gaps, const uint32_t* __restrict__ cand, uint64_t ncand,
+                                                                   uint32_t* res, unsigned long long* counters)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t c = (uint64_t)blockIdx.x * FIND_WAVES + (threadIdx.x >> 6);
+    if (c >= ncand) return; /* (uniform in the wave; the kernel has no workgroup barrier) */
+    const mtg_run g = gaps[cand[c]];
+    const int k = ix.k;
+    const uint64_t mk = kmask(k), mk1 = kmask(k - 1), cmpl = 0xAAAAAAAAAAAAAAAAULL & mk;
+    const uint64_t* w = words + word_off[g.seq];
+    const uint32_t L = len[g.seq], e = g.start + g.length, r = (uint32_t)(k - 1) - g.length, rp = e + r;
+    bool right_ok = true; /* r = 0: the k-mer at e, present */
+    if (r) {
+        right_ok = (uint64_t)rp + (uint32_t)k <= L;
+        if (right_ok && bad) { /* as k_profile: the k bits of the characters rp .. rp + k - 1 */
+            const uint64_t* bw = bad + word_off[g.seq];
+            const uint32_t sh = rp & 63u;
+            uint64_t m = bw[rp >> 6] >> sh;
+            if (sh + (uint32_t)k > 64u) m |= bw[(rp >> 6) + 1] << (64u - sh);
+            right_ok = (m & ((1ull << k) - 1ull)) == 0;
+        }
+    }
+    uint32_t out = 0;
+    if (right_ok) {
+        const uint64_t lk = le_kmer(w, g.start - 1u, mk), ek = le_kmer(w, e, mk), rk = r ? le_kmer(w, rp, mk) : ek;
+        uint32_t lines = 0;
+        bool mine = true;
+        if (lane < 2u) {
+            Kmer x;
+            x.r = (lane ? ek : lk) ^ cmpl;
+            x.f = revcomp(x.r, k);
+            mine = lane ? adj_left(ix, x, mk1, lines).in != 0 : adj_right_t(ix.adj, x, mk1, lines).out != 0;
+        }
+        const bool degrees = __ballot(!mine) == 0ull;
+        if (r == 0 || degrees) {
+            const uint32_t half = lane >> 5, j = lane & 31u;
+            int found = -1;
+            for (uint32_t it = 0; it < 10u && found < 0; it++) {
+                const uint32_t si = 2u * it + half, n = si < 4u ? 1u : 2u;
+                /* codes of A, C, G, T in that order: 0, 1, 3, 2; the first inserted nucleotide lowest */
+                const uint32_t ins = si < 4u ? (0xB4u >> (2u * si)) & 3u : ((0xB4u >> (2u * ((si - 4u) >> 2))) & 3u) | (((0xB4u >> (2u * ((si - 4u) & 3u))) & 3u) << 2);
+                const unsigned __int128 text = (unsigned __int128)lk | ((unsigned __int128)ins << (2 * k)) | ((unsigned __int128)rk << (2 * (k + (int)n)));
+                bool solid = true;
+                if (j < (uint32_t)k) {
+                    Kmer x;
+                    x.r = ((uint64_t)(text >> (2u * j)) & mk) ^ cmpl;
+                    x.f = revcomp(x.r, k);
+                    solid = abundance(ix, x, lines) != 0;
+                }
+                const unsigned long long bal = __ballot(solid);
+                if ((uint32_t)bal == 0xFFFFFFFFu) found = (int)(2u * it);
+                else if ((uint32_t)(bal >> 32) == 0xFFFFFFFFu) found = (int)(2u * it + 1u);
+            }
+            if (found >= 0) out = 1u | (1u << 1) | ((uint32_t)found << 8);
+            else if (degrees) out = 1u;
+        }
+    }
+    if (lane == 0) {
+        res[c] = out;
+        if (out) atomicAdd(&counters[2 + ((out >> 1) & 1u) * 2u + (r ? 1u : 0u)], 1ull);
+    }
+}
+/* the records of the calls: call j is candidate sel[j] */
+__global__ void __launch_bounds__(RUNS_BLOCK) k_find_emit(const mtg_run* __restrict__ gaps, const uint32_t* __restrict__ cand, const uint32_t* __restrict__ res,
+                                                         const uint32_t* __restrict__ sel, uint64_t n, int k, mtg_find_call* calls)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t c = sel[j], o = res[c];
+    const mtg_run g = gaps[cand[c]];
+    const uint32_t e = g.start + g.length, r = (uint32_t)(k - 1) - g.length, kind = (o >> 1) & 1u;
+    mtg_find_call q;
+    q.seq = g.seq; q.pos = kind ? e - 1u : e - 1u + r; q.kind = kind; q.repeat = r; q.left = g.start - 1u; q.right = e + r; q.ins = o >> 8;
+    calls[j] = q;
 }
 
 /* dependent chains of random line reads: the access pattern of the simple-path walk.  LINE = bytes read per step (16..128) */
@@ -787,7 +920,7 @@ int profile_run(const mtg_index* idx, const uint64_t* words, size_t nwords, cons
     const dim3 grid((unsigned)std::min<size_t>(nseq, 256 * 16));
     HIP_TRY(hipEventRecord(e0, 0));
     hipLaunchKernelGGL(k_profile, grid, dim3(SCAN_TILE), 0, 0, idx->dev, pw, po, pl, nseq, pbad, ppo, pout, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt);
-    hipLaunchKernelGGL(k_profile_count, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_profile_count<false>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_cnt.as<uint32_t>());
     hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + 4);
     HIP_TRY(hipEventRecord(e1, 0));
     HIP_TRY(hipGetLastError());
@@ -801,7 +934,7 @@ int profile_run(const mtg_index* idx, const uint64_t* words, size_t nwords, cons
     if (total) {
         HIP_TRY(hipMemset(pr, 0, (size_t)total * sizeof(mtg_run)));
         HIP_TRY(hipEventRecord(e2, 0));
-        hipLaunchKernelGGL(k_profile_write, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_before.as<uint64_t>(), pr, total);
+        hipLaunchKernelGGL(k_profile_write<false>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_before.as<uint64_t>(), pr, total);
         hipLaunchKernelGGL(k_profile_finish, dim3((unsigned)std::min<uint64_t>((total + RUNS_BLOCK - 1) / RUNS_BLOCK, 256 * 16)), dim3(RUNS_BLOCK), 0, 0, pr, total, cnt + 4);
         HIP_TRY(hipEventRecord(e3, 0));
         HIP_TRY(hipGetLastError());
@@ -815,6 +948,125 @@ int profile_run(const mtg_index* idx, const uint64_t* words, size_t nwords, cons
     if (!device_ptrs && out) HIP_TRY(hipMemcpy(out, pout, npos_total * 4, hipMemcpyDeviceToHost));
     *n_runs = (size_t)total;
     if (st) { st->n_positions = c[0]; st->n_valid = c[1]; st->n_present = c[2]; st->n_runs = total; st->longest_run = total ? c[5] : 0; st->kernel_ms = (double)ms0 + (double)ms1; }
+    return MTG_OK;
+}
+
+/* the indices of the non-zero marks in ascending order (k_mark_count, k_profile_seq_scan, k_mark_index): *total = how many; index receives
+ * min(*total, cap) of them (allocated here).  Synchronises once, to read the total */
+static int mark_compact(const uint32_t* mark, uint64_t n, DevBuf& d_blk_cnt, DevBuf& d_blk_before, unsigned long long* d_tot, DevBuf& index, uint64_t cap, uint64_t* total)
+{
+    const unsigned nb = (unsigned)((n + RUNS_BLOCK - 1) / RUNS_BLOCK);
+    HIP_TRY(d_blk_cnt.alloc((size_t)nb * 4)); HIP_TRY(d_blk_before.alloc((size_t)nb * 8));
+    hipLaunchKernelGGL(k_mark_count, dim3(nb), dim3(RUNS_BLOCK), 0, 0, mark, n, d_blk_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_blk_cnt.as<uint32_t>(), (size_t)nb, d_blk_before.as<uint64_t>(), d_tot);
+    HIP_TRY(hipGetLastError());
+    unsigned long long t = 0;
+    HIP_TRY(hipMemcpy(&t, d_tot, 8, hipMemcpyDeviceToHost));
+    *total = t;
+    const uint64_t keep = std::min<uint64_t>(t, cap);
+    HIP_TRY(index.alloc((size_t)keep * 4));
+    if (keep) hipLaunchKernelGGL(k_mark_index, dim3(nb), dim3(RUNS_BLOCK), 0, 0, mark, n, d_blk_before.as<uint64_t>(), index.as<uint32_t>(), keep);
+    HIP_TRY(hipGetLastError());
+    return MTG_OK;
+}
+
+/* `find` for homozygous insertions over packed sequences (mtg_index_find_homo_sequences / _packed_device).  device_ptrs = 0: words / word_off /
+ * len / bad are host arrays and calls host memory; 1: all of them device memory (nwords unused, bad null) */
+int find_homo_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
+                  mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_stats* st)
+{
+    if (int rc = use_device_of(idx)) return rc;
+    if (!idx || !idx->dev.bloom.bits) { set_error("the index has no Bloom filter (MTG_BLOOM_BITS=0)"); return MTG_ERR_ARG; }
+    *n_calls = 0;
+    if (st) *st = mtg_find_stats{};
+    if (nseq == 0) return MTG_OK;
+    const int k = idx->dev.k;
+    if (max_repeat > k - 2) max_repeat = k - 2;
+    DevBuf d_w, d_o, d_l, d_bad, d_v, d_p, d_cnt, d_before, d_c, d_gaps, d_mark, d_blk_cnt, d_blk_before, d_cand, d_res, d_sel, d_calls;
+    const uint64_t *pw = words, *po = word_off, *pbad = bad;
+    const uint32_t* pl = len;
+    if (!device_ptrs) {
+        HIP_TRY(d_w.alloc(nwords * 8)); HIP_TRY(d_o.alloc(nseq * 8)); HIP_TRY(d_l.alloc(nseq * 4));
+        HIP_TRY(hipMemcpy(d_w.p, words, nwords * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_o.p, word_off, nseq * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_l.p, len, nseq * 4, hipMemcpyHostToDevice));
+        pw = d_w.as<uint64_t>(); po = d_o.as<uint64_t>(); pl = d_l.as<uint32_t>();
+        if (bad) { HIP_TRY(d_bad.alloc(nwords * 8)); HIP_TRY(hipMemcpy(d_bad.p, bad, nwords * 8, hipMemcpyHostToDevice)); pbad = d_bad.as<uint64_t>(); }
+    } else { /* as profile_run: how far the planes reach */
+        std::vector<uint64_t> ho(nseq);
+        std::vector<uint32_t> hl(nseq);
+        HIP_TRY(hipMemcpy(ho.data(), word_off, nseq * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hl.data(), len, nseq * 4, hipMemcpyDeviceToHost));
+        nwords = 0;
+        for (size_t s = 0; s < nseq; s++) nwords = std::max<size_t>(nwords, (size_t)ho[s] + hl[s] / 64 + 1);
+    }
+    HIP_TRY(d_v.alloc(nwords * 8)); HIP_TRY(d_p.alloc(nwords * 8));
+    HIP_TRY(d_cnt.alloc(nseq * 4)); HIP_TRY(d_before.alloc(nseq * 8));
+    HIP_TRY(d_c.alloc(128));
+    HIP_TRY(hipMemset(d_c.p, 0, 128));
+    unsigned long long* cnt = d_c.as<unsigned long long>(); /* [0..2] k_profile's counters, [4] gaps of any kind, [5] the longest, [6] candidates, [7] calls, [8] gaps seen, [10..13] the four kinds */
+    EventSet events;
+    hipEvent_t ev[8];
+    for (hipEvent_t& e : ev) HIP_TRY(events.make(e));
+    const dim3 grid((unsigned)std::min<size_t>(nseq, 256 * 16));
+    unsigned long long c[16];
+    float ms = 0, part = 0;
+    /* 1. the planes, the gaps counted */
+    HIP_TRY(hipEventRecord(ev[0], 0));
+    hipLaunchKernelGGL(k_profile, grid, dim3(SCAN_TILE), 0, 0, idx->dev, pw, po, pl, nseq, pbad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt);
+    hipLaunchKernelGGL(k_profile_count<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + 4);
+    HIP_TRY(hipEventRecord(ev[1], 0));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(c, d_c.p, 128, hipMemcpyDeviceToHost));
+    HIP_TRY(hipEventElapsedTime(&part, ev[0], ev[1])); ms += part;
+    const uint64_t n_gaps_all = c[4];
+    if (n_gaps_all > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 gaps"); return MTG_ERR_ARG; }
+    uint64_t n_cand = 0, total = 0;
+    if (n_gaps_all) {
+        /* 2. the gaps written, the candidates marked and listed in order */
+        HIP_TRY(d_gaps.alloc((size_t)n_gaps_all * sizeof(mtg_run)));
+        HIP_TRY(hipMemset(d_gaps.p, 0, (size_t)n_gaps_all * sizeof(mtg_run)));
+        HIP_TRY(d_mark.alloc((size_t)n_gaps_all * 4));
+        const unsigned gb = (unsigned)((n_gaps_all + RUNS_BLOCK - 1) / RUNS_BLOCK);
+        HIP_TRY(hipEventRecord(ev[2], 0));
+        hipLaunchKernelGGL(k_profile_write<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_before.as<uint64_t>(), d_gaps.as<mtg_run>(), n_gaps_all);
+        hipLaunchKernelGGL(k_profile_finish, dim3(std::min(gb, 256u * 16u)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, cnt + 4);
+        hipLaunchKernelGGL(k_find_mark, dim3(gb), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, k, max_repeat, d_mark.as<uint32_t>(), cnt + 8);
+        if (int rc = mark_compact(d_mark.as<uint32_t>(), n_gaps_all, d_blk_cnt, d_blk_before, cnt + 6, d_cand, ~0ull, &n_cand)) return rc;
+        HIP_TRY(hipEventRecord(ev[3], 0));
+    }
+    if (n_cand) {
+        /* 3. the observers, one wave per candidate; the calls listed in order and written */
+        HIP_TRY(d_res.alloc((size_t)n_cand * 4));
+        HIP_TRY(hipEventRecord(ev[4], 0));
+        hipLaunchKernelGGL(k_find_assemble, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, pw, po, pl, pbad, d_gaps.as<mtg_run>(),
+                           d_cand.as<uint32_t>(), n_cand, d_res.as<uint32_t>(), cnt + 8);
+        if (int rc = mark_compact(d_res.as<uint32_t>(), n_cand, d_blk_cnt, d_blk_before, cnt + 7, d_sel, cap, &total)) return rc;
+        const uint64_t keep = std::min<uint64_t>(total, cap);
+        mtg_find_call* pc = calls;
+        if (keep) {
+            if (!device_ptrs) { HIP_TRY(d_calls.alloc((size_t)keep * sizeof(mtg_find_call))); pc = d_calls.as<mtg_find_call>(); }
+            hipLaunchKernelGGL(k_find_emit, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(),
+                               d_res.as<uint32_t>(), d_sel.as<uint32_t>(), keep, k, pc);
+        }
+        HIP_TRY(hipEventRecord(ev[5], 0));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventSynchronize(ev[5]));
+        if (keep && !device_ptrs) HIP_TRY(hipMemcpy(calls, pc, (size_t)keep * sizeof(mtg_find_call), hipMemcpyDeviceToHost));
+        HIP_TRY(hipEventElapsedTime(&part, ev[4], ev[5])); ms += part;
+    }
+    if (n_gaps_all) {
+        HIP_TRY(hipEventSynchronize(ev[3]));
+        HIP_TRY(hipEventElapsedTime(&part, ev[2], ev[3])); ms += part;
+    }
+    HIP_TRY(hipMemcpy(c, d_c.p, 128, hipMemcpyDeviceToHost));
+    *n_calls = (size_t)total;
+    if (st) {
+        st->n_positions = c[0]; st->n_gaps = c[8]; st->n_candidates = n_cand;
+        st->n_homo_clean = c[10]; st->n_homo_fuzzy = c[11]; st->n_small_clean = c[12]; st->n_small_fuzzy = c[13];
+        st->kernel_ms = (double)ms;
+    }
     return MTG_OK;
 }
 

@@ -130,6 +130,12 @@ __attribute__((weak)) int profile_run(const mtg_index*, const uint64_t*, size_t,
     set_error("this build has no device code for the profile");
     return MTG_ERR_NO_DEVICE;
 }
+__attribute__((weak)) int find_homo_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, int, mtg_find_call*, size_t, size_t*, int,
+                                        mtg_find_stats*)
+{
+    set_error("this build has no device code for find");
+    return MTG_ERR_NO_DEVICE;
+}
 
 /* ------------------------------------------------------------------------------------------------ index from reads */
 static inline bool nt_bad(unsigned char c) { return (c >> 3) & 1; } /* gatb: bit 3 of the ASCII code flags 'N' */
@@ -1859,29 +1865,40 @@ int mtg_index_scan_sequences(const mtg_index* idx, const char* const* seqs, size
     return MTG_OK;
 }
 
-int mtg_index_profile_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, uint32_t* const* out, mtg_run* runs, size_t runs_cap, size_t* n_runs,
-                                mtg_profile_stats* st)
+/* The scan's packing of strings, and next to it one bit per character that is no nucleotide (the device tells which k-mers cover one):
+ * word offsets, lengths, the offset of every sequence's first position, the two word arrays.  Returns false (error set) on a bad argument. */
+static bool pack_with_bad_bits(const char* const* seqs, size_t nseq, int k, uint32_t* const* out, std::vector<uint64_t>& off, std::vector<uint32_t>& len, std::vector<uint64_t>& pos_off,
+                               uint64_t& npos, std::vector<uint64_t>& words, std::vector<uint64_t>& bad)
 {
-    if (!idx || !n_runs || (nseq && !seqs) || (runs_cap && !runs)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
-    const int k = idx->dev.k;
-    std::vector<uint64_t> off(nseq), pos_off(nseq);
-    std::vector<uint32_t> len(nseq);
-    uint64_t nw = 0, npos = 0;
+    off.assign(nseq, 0); pos_off.assign(nseq, 0); len.assign(nseq, 0);
+    uint64_t nw = 0;
+    npos = 0;
     for (size_t s = 0; s < nseq; s++) {
-        if (!seqs[s] || (out && !out[s] && strlen(seqs[s]) >= (size_t)k)) { mtgi::set_error("sequence %zu: null pointer", s); return MTG_ERR_ARG; }
+        if (!seqs[s] || (out && !out[s] && strlen(seqs[s]) >= (size_t)k)) { mtgi::set_error("sequence %zu: null pointer", s); return false; }
         const size_t l = strlen(seqs[s]);
-        if (l > 0xFFFFFFFFull) { mtgi::set_error("sequence %zu: longer than 2^32 - 1", s); return MTG_ERR_ARG; }
+        if (l > 0xFFFFFFFFull) { mtgi::set_error("sequence %zu: longer than 2^32 - 1", s); return false; }
         len[s] = (uint32_t)l; off[s] = nw; nw += (len[s] + 31) / 32 + 2;
         pos_off[s] = npos; npos += len[s] < (uint32_t)k ? 0 : len[s] - (uint32_t)k + 1;
     }
-    /* the scan's packing, and next to it one bit per character that is no nucleotide: the device tells which k-mers cover one */
-    std::vector<uint64_t> words(nw + 2, 0), bad(nw + 2, 0);
+    words.assign(nw + 2, 0); bad.assign(nw + 2, 0);
     for (size_t s = 0; s < nseq; s++)
         for (uint32_t i = 0; i < len[s]; i++) {
             const unsigned char ch = (unsigned char)seqs[s][i];
             words[off[s] + (i >> 5)] |= (uint64_t)nt_code(ch) << (2 * (i & 31));
             if (mtgi::nt_bad(ch)) bad[off[s] + (i >> 6)] |= 1ull << (i & 63);
         }
+    return true;
+}
+
+int mtg_index_profile_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, uint32_t* const* out, mtg_run* runs, size_t runs_cap, size_t* n_runs,
+                                mtg_profile_stats* st)
+{
+    if (!idx || !n_runs || (nseq && !seqs) || (runs_cap && !runs)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    const int k = idx->dev.k;
+    std::vector<uint64_t> off, pos_off, words, bad;
+    std::vector<uint32_t> len;
+    uint64_t npos = 0;
+    if (!pack_with_bad_bits(seqs, nseq, k, out, off, len, pos_off, npos, words, bad)) return MTG_ERR_ARG;
     std::vector<uint32_t> flat(out ? npos : 0);
     int rc = mtgi::profile_run(idx, words.data(), words.size(), off.data(), len.data(), nseq, bad.data(), pos_off.data(), npos, out ? flat.data() : nullptr, runs, runs_cap, n_runs, 0, st);
     if (rc) return rc;
@@ -1897,6 +1914,24 @@ int mtg_index_profile_packed_device(const mtg_index* idx, const uint64_t* d_word
 {
     if (!idx || !n_runs || (nseq && (!d_words || !d_word_off || !d_len)) || (d_out && !d_pos_off) || (runs_cap && !d_runs)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
     return mtgi::profile_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, d_pos_off, 0, d_out, d_runs, runs_cap, n_runs, 1, st);
+}
+
+int mtg_index_find_homo_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_stats* st)
+{
+    if (!idx || !n_calls || (nseq && !seqs) || (cap && !calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
+    std::vector<uint64_t> off, pos_off, words, bad;
+    std::vector<uint32_t> len;
+    uint64_t npos = 0;
+    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, off, len, pos_off, npos, words, bad)) return MTG_ERR_ARG;
+    return mtgi::find_homo_run(idx, words.data(), words.size(), off.data(), len.data(), nseq, bad.data(), max_repeat, calls, cap, n_calls, 0, st);
+}
+int mtg_index_find_homo_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
+                                      mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_stats* st)
+{
+    if (!idx || !n_calls || (nseq && (!d_words || !d_word_off || !d_len)) || (cap && !d_calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
+    return mtgi::find_homo_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, d_calls, cap, n_calls, 1, st);
 }
 
 int mtg_nw_matches(const char* const* a, const char* const* b, size_t n, uint32_t* matches)

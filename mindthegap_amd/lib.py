@@ -97,6 +97,21 @@ class ProfileStats(C.Structure):
     _fields_ = [("n_positions", C.c_uint64), ("n_valid", C.c_uint64), ("n_present", C.c_uint64), ("n_runs", C.c_uint64), ("longest_run", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
+class FindStats(C.Structure):
+    _fields_ = [("n_positions", C.c_uint64), ("n_gaps", C.c_uint64), ("n_candidates", C.c_uint64), ("n_homo_clean", C.c_uint64), ("n_homo_fuzzy", C.c_uint64),
+                ("n_small_clean", C.c_uint64), ("n_small_fuzzy", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+# a call of `find` for homozygous insertions (mtg_find_call): kind 0 = insertion site, 1 = insertion of 1-2 nt; ins indexes FIND_INSERTIONS
+CALL_DTYPE = np.dtype([("seq", np.uint32), ("pos", np.uint32), ("kind", np.uint32), ("repeat", np.uint32), ("left", np.uint32), ("right", np.uint32), ("ins", np.uint32)])
+FIND_INSERTIONS = ("A", "C", "G", "T", "AA", "AC", "AG", "AT", "CA", "CC", "CG", "CT", "GA", "GC", "GG", "GT", "TA", "TC", "TG", "TT")
+
+
+def decode_find_calls(buf, n):
+    """the leading n records of a buffer of mtg_find_call (bytes, or a uint32 array of 7 words a record) as a CALL_DTYPE array"""
+    return np.frombuffer(buf, dtype=CALL_DTYPE, count=n).copy()
+
+
 # a run of absent k-mers (mtg_run): flags bit 0 / bit 1 = a present position right before / right behind it
 RUN_DTYPE = np.dtype([("seq", np.uint32), ("start", np.uint32), ("length", np.uint32), ("flags", np.uint32)])
 
@@ -197,6 +212,9 @@ def _bind(lib):
     lib.mtg_index_profile_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, P(C.c_size_t),
                                                     P(ProfileStats)]
     lib.mtg_profile_main.argtypes = [C.c_int, P(C.c_char_p)]
+    lib.mtg_index_find_homo_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindStats)]
+    lib.mtg_index_find_homo_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindStats)]
+    lib.mtg_find_main.argtypes = [C.c_int, P(C.c_char_p)]
     lib.mtg_default_params.argtypes = [P(Params)]
     lib.mtg_default_params.restype = None
     lib.mtg_fill_batch.argtypes = [C.c_void_p, P(Params), P(CGap), C.c_size_t, P(C.c_void_p)]
@@ -517,6 +535,30 @@ class Index:
         _check(self.lib.mtg_index_profile_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, pos_off_ptr, out_ptr, runs_ptr, runs_cap, C.byref(total), C.byref(st)))
         return total.value, {f[0]: getattr(st, f[0]) for f in ProfileStats._fields_}
 
+    def find_homo_sequences(self, seqs, max_repeat=5, cap=None):
+        """`find` for homozygous insertions: the insertion sites and the insertions of 1-2 nt of seqs against the graph; returns (calls as a
+        CALL_DTYPE array in the order of the scan, stats dict).  cap: give the array that capacity and return the leading calls
+        (stats["n_calls"] is always the total); by default it is sized to hold them all."""
+        n = len(seqs)
+        arr = (C.c_char_p * n)(*[s.encode() for s in seqs])
+        room = 1024 if cap is None else int(cap)
+        while True:
+            calls = np.zeros(room, dtype=CALL_DTYPE)
+            total, st = C.c_size_t(), FindStats()
+            _check(self.lib.mtg_index_find_homo_sequences(self.h, arr, n, max_repeat, calls.ctypes.data if room else None, room, C.byref(total), C.byref(st)))
+            if cap is not None or total.value <= room:
+                break
+            room = total.value
+        stats = {f[0]: getattr(st, f[0]) for f in FindStats._fields_}
+        stats["n_calls"] = total.value
+        return calls[:min(total.value, room)], stats
+
+    def find_homo_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap):
+        """the same on packed sequences in device memory (pointers as integers; calls_ptr: device array of cap mtg_find_call); returns (total calls, stats dict)"""
+        total, st = C.c_size_t(), FindStats()
+        _check(self.lib.mtg_index_find_homo_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap, C.byref(total), C.byref(st)))
+        return total.value, {f[0]: getattr(st, f[0]) for f in FindStats._fields_}
+
     def stage_a(self, sources, targets, params=None):
         """Contigs of every gap (gatb IterativeExtensions::construct_linear_seqs, src/Filler.cpp:884)."""
         params = params or FillParams()
@@ -807,6 +849,12 @@ def profile_main(argv):
     """`MindTheGap profile <argv>`: writes <out>.absent.bed and <out>.profile.txt; returns the exit code."""
     arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
     return load_library().mtg_profile_main(len(argv), arr)
+
+
+def find_main(argv):
+    """`MindTheGap find <argv>`: writes <out>.breakpoints and <out>.othervariants.vcf; returns the exit code."""
+    arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
+    return load_library().mtg_find_main(len(argv), arr)
 
 
 def nw_matches(pairs):
