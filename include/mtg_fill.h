@@ -174,6 +174,33 @@ int mtg_index_find_homo_sequences(const mtg_index* idx, const char* const* seqs,
 int mtg_index_find_homo_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
                                       mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_stats* st);
 
+/* `find` for heterozygous insertions: the reference's k-mer observer FindHeteroInsertion (src/FindHeteroInsertion.hpp:46-174) and no other, as
+ * it runs under -hete-only and -insert-only.  At a valid position p whose k-mer has in-degree 2 and a prefix (k-1)-mer that is not repeated,
+ * it looks for the first i in 0 .. max_repeat whose history slot p - k + i holds a k-mer of out-degree 2 with a suffix (k-1)-mer that is not
+ * repeated (the history is the reference's ring of 256 slots, written at valid positions only: see csrc/mtg_find_het.h).  With the k
+ * nucleotides at p + i as the right k-mer it is an insertion of 1-2 nt when one of the 20 strings assembles (the rule of
+ * mtg_index_find_homo_sequences), else a site unless more than branching_filter of the 100 history slots before the window hold a k-mer with a
+ * degree above 1 (branching_filter < 0: no filter).  A site silences the observer for the next max_repeat valid positions.  Records as above:
+ *   kind   2 heterozygous site, 3 heterozygous insertion of 1-2 nt
+ *   pos    p - 1 for an insertion, p - 1 + i for a site;  repeat = i;  left = position of the left k-mer's text;  right = p + i;  ins as above
+ * in the order of the scan (ascending seq, then p).  repeated[s] holds one byte (0 / 1) per (k-1)-mer position of sequence s, len - k + 2 of
+ * them -- what mtg_index_scan_sequences returns for an index of k - 1 that holds the repeated (k-1)-mers; repeated == NULL: nothing is
+ * repeated (entries of sequences shorter than k are not read).  The reference asks a Bloom filter of the repeated (k-1)-mers; a false positive
+ * of it can silence a site there that is called here.  max_repeat, cap, *n_calls, calls, st and the character rule as for
+ * mtg_index_find_homo_sequences. */
+typedef struct mtg_find_het_stats {
+    uint64_t n_positions, n_candidates /* positions where a qualifying i exists, `recent` aside */, n_raw_sites /* of those, sites judged as if nothing were recent */;
+    uint64_t n_filtered /* sites refused by the branching filter */, n_suppressed /* sites and insertions silenced by a site before them */;
+    uint64_t n_het_clean, n_het_fuzzy /* sites called, i = 0 / i > 0 */, n_het_small /* insertions of 1-2 nt called */;
+    double kernel_ms;
+} mtg_find_het_stats;
+int mtg_index_find_het_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, const uint8_t* const* repeated, int max_repeat, int branching_filter,
+                                 mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_het_stats* st);
+/* same on 2-bit packed sequences already in DEVICE memory (no invalid positions); d_repeat_bits: the repeat plane in the layout of
+ * mtg_index_scan_packed_device's output for an index of k - 1 (bit q % 64 of d_repeat_bits[word_off[s] + q / 64]), or NULL; d_calls is a device array */
+int mtg_index_find_het_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, const uint64_t* d_repeat_bits,
+                                     int max_repeat, int branching_filter, mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_het_stats* st);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Gap filling = Filler::gapFillFromSource over a batch of gaps.
  * ---------------------------------------------------------------------------------------------------------- */
@@ -451,9 +478,12 @@ int mtg_fill_main_on_index(mtg_index* idx, int argc, const char* const* argv);
  * name, start, start + length, length, L|R|LR|. (k-mer start positions, 0-based, half-open; name = the FASTA header up to the first blank),
  * and prefix.profile.txt, the statistics as `key : value` lines.  Returns 0 / 1; nothing is written unless the whole profile succeeded. */
 int mtg_profile_main(int argc, const char* const* argv);
-/* `MindTheGap find (-in reads | -graph container) -ref genome.fa -homo-insertions [-max-rep 5] [-kmer-size -abundance-min -abundance-max]
- * [-out prefix]`: the part of the reference's `find` that mtg_index_find_homo_sequences covers.  Without -homo-insertions it stops with a
- * message that names what is not built (SNPs, deletions, heterozygous sites, -bed) and returns 1.  Writes prefix.breakpoints (writeBreakpoint,
+/* `MindTheGap find (-in reads | -graph container) -ref genome.fa (-homo-insertions | -hete-only | -insert-only) [-max-rep 5] [-het-max-occ 1]
+ * [-branching-filter 15] [-kmer-size -abundance-min -abundance-max] [-out prefix]`: the part of the reference's `find` that
+ * mtg_index_find_homo_sequences (-homo-insertions), mtg_index_find_het_sequences plus the homozygous insertions of 1-2 nt (-hete-only, as the
+ * reference's option of that name) or both in full (-insert-only, calls merged in detection order) cover.  The repeat flags of the heterozygous
+ * observer come from an index of the genome file at k - 1 with abundance_min = het_max_occ + 1 (k >= 12).  Without one of the three flags it stops
+ * with a message that names what is not built (SNPs, deletions, -bed) and returns 1.  Writes prefix.breakpoints (writeBreakpoint,
  * src/FindBreakpoints.hpp:640-658) and prefix.othervariants.vcf (header of src/Finder.cpp:513-541, records of writeIndel); ids bkptN count
  * from 1 in detection order across both files; the REPEATED field stays empty (the reference fills it from a Bloom filter of the genome's
  * (k-1)-mers, whose false positives are not reproducible).  Prints the Results block of the reference's summary.  Returns 0 / 1; nothing is

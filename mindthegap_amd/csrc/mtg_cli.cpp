@@ -1440,14 +1440,16 @@ int profile_main(int argc, const char* const* argv)
     return 0;
 }
 
-/* `MindTheGap find -homo-insertions`: the homozygous insertion sites and the insertions of 1-2 nt of a reference genome against the graph
- * (mtg_index_find_homo_sequences), in the reference's two files.  Both are written once the whole scan is there. */
+/* `MindTheGap find -homo-insertions | -hete-only | -insert-only`: the insertion sites and the insertions of 1-2 nt of a reference genome against
+ * the graph, homozygous (mtg_index_find_homo_sequences), heterozygous (mtg_index_find_het_sequences) or both, in the reference's two files.
+ * Both are written once the whole scan is there. */
 int find_main(int argc, const char* const* argv)
 {
     std::string in, graph, ref, out = "MindTheGap_Expe"; /* the reference names it after the date (src/Finder.cpp: MindTheGap_Expe-<date>) */
-    int k = 31, abundance_min = -1, abundance_max = 0, max_repeat = 5;
-    bool homo_only = false;
-    const char* usage = "Usage: MindTheGap find (-in <reads> | -graph <container>) -ref <genome.fa> -homo-insertions [-max-rep 5] [-kmer-size 31] [-abundance-min auto] [-abundance-max 0] [-out <prefix>]\n";
+    int k = 31, abundance_min = -1, abundance_max = 0, max_repeat = 5, het_max_occ = 1, branching_filter = 15;
+    bool homo_flag = false, hete_only = false, insert_only = false;
+    const char* usage = "Usage: MindTheGap find (-in <reads> | -graph <container>) -ref <genome.fa> (-homo-insertions | -hete-only | -insert-only) [-max-rep 5] [-het-max-occ 1] "
+                        "[-branching-filter 15] [-kmer-size 31] [-abundance-min auto] [-abundance-max 0] [-out <prefix>]\n";
     for (int i = 0; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&](std::string& dst) -> bool { if (i + 1 >= argc) return false; dst = argv[++i]; return true; };
@@ -1457,7 +1459,11 @@ int find_main(int argc, const char* const* argv)
         else if (a == "-graph") ok = val(graph);
         else if (a == "-ref") ok = val(ref);
         else if (a == "-out") ok = val(out);
-        else if (a == "-homo-insertions") homo_only = true;
+        else if (a == "-homo-insertions") homo_flag = true;
+        else if (a == "-hete-only") hete_only = true;
+        else if (a == "-insert-only") insert_only = true;
+        else if (a == "-het-max-occ") { ok = val(v); het_max_occ = atoi(v.c_str()); }
+        else if (a == "-branching-filter") { ok = val(v); branching_filter = atoi(v.c_str()); }
         else if (a == "-max-rep") { ok = val(v); max_repeat = atoi(v.c_str()); }
         else if (a == "-kmer-size") { ok = val(v); k = atoi(v.c_str()); }
         else if (a == "-abundance-min") { ok = val(v); abundance_min = v == "auto" ? -1 : atoi(v.c_str()); }
@@ -1468,14 +1474,23 @@ int find_main(int argc, const char* const* argv)
         }
         if (!ok) { fprintf(stderr, "EXCEPTION: missing value for option '%s'\n", a.c_str()); return 1; }
     }
-    if (!homo_only) {
-        fprintf(stderr, "EXCEPTION: this build of find detects homozygous insertions only (sites and insertions of 1-2 nt): SNPs, deletions, heterozygous sites and -bed are "
-                        "not built.  Pass -homo-insertions to run that subset; its output is not the reference's default find.\n%s", usage);
+    /* -hete-only keeps the two observers of homozygous insertions of 1-2 nt, as the reference's option of that name does (_small_homo stays true,
+     * src/Finder.cpp:364-373,562-566): the gap layer runs and its sites are left out.  A gap goes to the site observers only when the small ones
+     * did not call it, so the calls of 1-2 nt are the same with and without them */
+    const bool run_homo = homo_flag || insert_only || hete_only, run_het = hete_only || insert_only, homo_sites = homo_flag || insert_only;
+    if (!run_homo && !run_het) {
+        fprintf(stderr, "EXCEPTION: this build of find detects insertions only (sites and insertions of 1-2 nt): SNPs, deletions and -bed are not built, and heterozygous "
+                        "insertions are found only under -hete-only or -insert-only.  Pass -homo-insertions, -hete-only or -insert-only to run that subset; only -insert-only "
+                        "is a configuration of the reference, none of them is its default find.\n%s", usage);
         return 1;
     }
     if (graph.empty() == in.empty()) { fprintf(stderr, "EXCEPTION: options -graph and -in are incompatible, but at least one of these is mandatory\n"); return 1; }
     if (ref.empty()) { fprintf(stderr, "EXCEPTION: option -ref is mandatory\n"); return 1; }
     if (max_repeat < 0) { fprintf(stderr, "EXCEPTION: -max-rep must not be negative\n"); return 1; }
+    if (het_max_occ < 1) het_max_occ = 1; /* src/Finder.cpp:316 */
+    const char* small_k = "EXCEPTION: -hete-only and -insert-only need a k-mer size of at least 12: the repeated (k-1)-mers of the genome are counted by an index of k - 1, and 11 is "
+                          "the smallest an index takes\n";
+    if (run_het && !in.empty() && k < 12) { fputs(small_k, stderr); return 1; }
     std::vector<std::pair<std::string, std::string>> recs;
     if (!read_sequences(ref, recs)) { fprintf(stderr, "EXCEPTION: cannot read %s\n", ref.c_str()); return 1; }
     mtg_index* idx = nullptr;
@@ -1483,20 +1498,65 @@ int find_main(int argc, const char* const* argv)
     if (rc) { fprintf(stderr, "EXCEPTION: %s\n", mtg_last_error()); return 1; }
     std::vector<const char*> seqs(recs.size());
     for (size_t i = 0; i < recs.size(); i++) seqs[i] = recs[i].second.c_str();
-    std::vector<mtg_find_call> calls(4096);
-    size_t n_calls = 0;
+    std::vector<mtg_find_call> calls(run_homo ? 4096 : 0), het_calls(run_het ? 4096 : 0);
+    size_t n_calls = 0, n_het = 0;
     mtg_find_stats st{};
+    mtg_find_het_stats hst{};
     const time_t t_start = time(0);
-    rc = mtg_index_find_homo_sequences(idx, seqs.data(), seqs.size(), max_repeat, calls.data(), calls.size(), &n_calls, &st);
-    if (!rc && n_calls > calls.size()) { /* the snprintf convention: once more with room for all of them */
-        calls.resize(n_calls);
+    const mtg_index_info info = idx->info;
+    k = info.k;
+    if (run_het && k < 12) { mtg_index_free(idx); fputs(small_k, stderr); return 1; }
+    if (run_homo) {
         rc = mtg_index_find_homo_sequences(idx, seqs.data(), seqs.size(), max_repeat, calls.data(), calls.size(), &n_calls, &st);
+        if (!rc && n_calls > calls.size()) { /* the snprintf convention: once more with room for all of them */
+            calls.resize(n_calls);
+            rc = mtg_index_find_homo_sequences(idx, seqs.data(), seqs.size(), max_repeat, calls.data(), calls.size(), &n_calls, &st);
+        }
+        if (!rc && n_calls > calls.size()) { rc = MTG_ERR_ARG; set_error("the number of calls changed between two calls"); }
+        if (!rc && !homo_sites) {
+            n_calls = (size_t)(std::remove_if(calls.begin(), calls.begin() + (ptrdiff_t)n_calls, [](const mtg_find_call& c) { return c.kind == 0; }) - calls.begin());
+            st.n_homo_clean = st.n_homo_fuzzy = 0;
+        }
+    }
+    if (run_het && !rc) {
+        /* the repeated (k-1)-mers of the genome (fillRefBloom, src/FindBreakpoints.hpp:956-1008, as an exact set): an index of the genome file at
+         * k - 1 that keeps what occurs at least het_max_occ + 1 times, and the genome scanned against it.  An index without a k-mer -- the
+         * normal case of a small genome -- means that nothing is repeated */
+        std::vector<std::vector<uint8_t>> flags;
+        std::vector<const uint8_t*> flag_ptrs;
+        mtg_index* ridx = nullptr;
+        rc = index_from_reads(ref.c_str(), k - 1, het_max_occ + 1, 0, &ridx);
+        if (!rc && ridx->info.nb_solid_kmers) {
+            flags.resize(recs.size());
+            std::vector<uint8_t*> outs(recs.size());
+            for (size_t i = 0; i < recs.size(); i++) { flags[i].assign(recs[i].second.size() + 2, 0); outs[i] = flags[i].data(); }
+            rc = mtg_index_scan_sequences(ridx, seqs.data(), seqs.size(), 1, outs.data(), nullptr);
+            flag_ptrs.assign(outs.begin(), outs.end());
+        }
+        if (ridx) mtg_index_free(ridx);
+        const uint8_t* const* rp = flag_ptrs.empty() ? nullptr : flag_ptrs.data();
+        if (!rc) rc = mtg_index_find_het_sequences(idx, seqs.data(), seqs.size(), rp, max_repeat, branching_filter, het_calls.data(), het_calls.size(), &n_het, &hst);
+        if (!rc && n_het > het_calls.size()) {
+            het_calls.resize(n_het);
+            rc = mtg_index_find_het_sequences(idx, seqs.data(), seqs.size(), rp, max_repeat, branching_filter, het_calls.data(), het_calls.size(), &n_het, &hst);
+        }
+        if (!rc && n_het > het_calls.size()) { rc = MTG_ERR_ARG; set_error("the number of calls changed between two calls"); }
     }
     const double seconds = difftime(time(0), t_start);
-    const mtg_index_info info = idx->info;
     mtg_index_free(idx);
-    if (rc || n_calls > calls.size()) { fprintf(stderr, "EXCEPTION: %s\n", rc ? mtg_last_error() : "the number of calls changed between two calls"); return 1; }
-    k = info.k;
+    if (rc) { fprintf(stderr, "EXCEPTION: %s\n", mtg_last_error()); return 1; }
+    if (run_het) {
+        /* both lists are in scan order; merged in the order of detection: a heterozygous call is made at position right - repeat, a homozygous one
+         * at right - repeat + 1, and at one position the k-mer observers run before the gap observers (src/FindBreakpoints.hpp:566-590) */
+        std::vector<mtg_find_call> all(n_calls + n_het);
+        const auto before = [](const mtg_find_call& a, const mtg_find_call& b) { /* a heterozygous, b homozygous */
+            return a.seq != b.seq ? a.seq < b.seq : a.right - a.repeat <= b.right - b.repeat + 1u;
+        };
+        size_t i = 0, j = 0, o = 0;
+        while (i < n_calls || j < n_het) all[o++] = (j < n_het && (i >= n_calls || before(het_calls[j], calls[i]))) ? het_calls[j++] : calls[i++];
+        calls.swap(all);
+        n_calls += n_het;
+    }
     std::string bkpt, vcf;
     {   /* Finder::writeVcfHeader, src/Finder.cpp:513-541 */
         const time_t now = time(nullptr);
@@ -1517,13 +1577,17 @@ int find_main(int argc, const char* const* argv)
         const std::string name = h.substr(0, h.find_first_of(" \t")), &s = recs[c.seq].second;
         const std::string left = kmer_string(s, c.left);
         const int id = (int)i + 1;
-        if (c.kind == 0) { /* writeBreakpoint, src/FindBreakpoints.hpp:640-658; the fuzzy right k-mer is the genome's text as it stands (FindInsertion.hpp:114) */
-            const std::string right = c.repeat ? s.substr(c.right, (size_t)k) : kmer_string(s, c.right);
-            appendf(bkpt, ">bkpt%i_%s_pos_%lli_fuzzy_%i_HOM %s left_kmer\n%s\n>bkpt%i_%s_pos_%lli_fuzzy_%i_HOM %s right_kmer\n%s\n", id, name.c_str(), (long long)c.pos + 1, (int)c.repeat, "",
-                    left.c_str(), id, name.c_str(), (long long)c.pos + 1, (int)c.repeat, "", right.c_str());
+        const bool het = c.kind >= 2;
+        if (c.kind == 0 || c.kind == 2) { /* writeBreakpoint, src/FindBreakpoints.hpp:640-658; the fuzzy right k-mer is the genome's text as it stands (FindInsertion.hpp:114), and so
+                                             is every right k-mer of the heterozygous observer (FindHeteroInsertion.hpp:76) */
+            const std::string right = (c.repeat || het) ? s.substr(c.right, (size_t)k) : kmer_string(s, c.right);
+            const char* type = het ? "HET" : "HOM";
+            appendf(bkpt, ">bkpt%i_%s_pos_%lli_fuzzy_%i_%s %s left_kmer\n%s\n>bkpt%i_%s_pos_%lli_fuzzy_%i_%s %s right_kmer\n%s\n", id, name.c_str(), (long long)c.pos + 1, (int)c.repeat, type, "",
+                    left.c_str(), id, name.c_str(), (long long)c.pos + 1, (int)c.repeat, type, "", right.c_str());
         } else { /* writeIndel, :679-702 */
             const std::string r(1, left[(size_t)(k - 1) - c.repeat]), alt = r + nucleo[c.ins < 20 ? c.ins : 0];
-            appendf(vcf, "%s\t%lli\tbkpt%i\t%s\t%s\t.\tPASS\tTYPE=INS;LEN=%i;FUZZY=%i\tGT\t1/1\n", name.c_str(), (long long)c.pos + 1, id, r.c_str(), alt.c_str(), (int)alt.size() - 1, (int)c.repeat);
+            appendf(vcf, "%s\t%lli\tbkpt%i\t%s\t%s\t.\tPASS\tTYPE=INS;LEN=%i;FUZZY=%i\tGT\t%s\n", name.c_str(), (long long)c.pos + 1, id, r.c_str(), alt.c_str(), (int)alt.size() - 1, (int)c.repeat,
+                    het ? "0/1" : "1/1");
         }
     }
     const auto write_file = [](const std::string& name, const std::string& text) -> bool {
@@ -1535,11 +1599,16 @@ int find_main(int argc, const char* const* argv)
     if (!write_file(out + ".breakpoints", bkpt) || !write_file(out + ".othervariants.vcf", vcf)) return 1;
     /* resumeResults, src/Finder.cpp:483-511: the counters this build has */
     printf("MindTheGap find\n    version                                  : %s\n    backend                                  : mindthegap_amd (HIP, gfx950)\n", MTG_VERSION);
-    printf("    Breakpoint detection options\n        max_repeat                               : %i\n        homo_insertions                          : yes\n"
-           "        hete_insertions                          : no\n        snp                                      : no\n        deletion                                 : no\n", max_repeat);
+    printf("    Breakpoint detection options\n        max_repeat                               : %i\n", max_repeat);
+    if (run_het) printf("        hetero_max_occ                           : %i\n        branching filter value                   : %i\n", het_max_occ, branching_filter);
+    printf("        homo_insertions                          : %s\n        hete_insertions                          : %s\n        snp                                      : no\n"
+           "        deletion                                 : no\n", homo_sites ? "yes" : "no", run_het ? "yes" : "no");
     printf("Results\n    Insertion breakpoints\n        homozygous                               : %llu\n            clean                                    : %llu\n"
            "            fuzzy                                    : %llu\n", (unsigned long long)(st.n_homo_clean + st.n_homo_fuzzy), (unsigned long long)st.n_homo_clean, (unsigned long long)st.n_homo_fuzzy);
+    if (run_het) printf("        heterozygous                             : %llu\n            clean                                    : %llu\n            fuzzy                                    : %llu\n",
+                        (unsigned long long)(hst.n_het_clean + hst.n_het_fuzzy), (unsigned long long)hst.n_het_clean, (unsigned long long)hst.n_het_fuzzy);
     printf("    Other variants\n        Homozygous insertions 1-2 bp size        : %llu\n", (unsigned long long)(st.n_small_clean + st.n_small_fuzzy));
+    if (run_het) printf("        Heterozygous insertions 1-2 bp size      : %llu\n", (unsigned long long)hst.n_het_small);
     printf("    Time                                     : %.1f s\n    Output files\n        breakpoint_file                          : %s.breakpoints\n        othervariants_file                       : %s.othervariants.vcf\n",
            seconds, out.c_str(), out.c_str());
     return 0;

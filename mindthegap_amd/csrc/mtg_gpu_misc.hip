@@ -14,6 +14,7 @@
 #include "mtg_gpu_common.h"
 #include "mtg_profile_runs.h"
 #include "mtg_find_gaps.h"
+#include "mtg_find_het.h"
 
 namespace mtgi {
 
@@ -301,11 +302,13 @@ __global__ void __launch_bounds__(SCAN_TILE) k_scan(Index ix, const uint64_t* __
  * exact confirmation), and for the confirmed positions the abundance and the neighbour masks of k_query, packed into one word per position
  * (include/mtg_fill.h).  bad = one bit per NUCLEOTIDE that is no nucleotide (bit i % 64 of bad[word_off[s] + i / 64]; nullptr: none): a k-mer
  * that covers one is invalid.  The valid and the present plane (bit layout of k_scan's output) go to vbits / pbits for k_profile_count /
- * k_profile_write.  counters: [0] positions, [1] valid, [2] present */
+ * k_profile_write.  counters: [0] positions, [1] valid, [2] present.  HET: three more planes for `find` for heterozygous insertions
+ * (mtg_find_het.h): in2 / out2 = present with in- / out-degree 2, br = present with a degree above 1; nothing else differs */
+template <bool HET>
 __global__ void __launch_bounds__(SCAN_TILE) k_profile(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off,
                                                        const uint32_t* __restrict__ len, size_t nseq, const uint64_t* __restrict__ bad,
                                                        const uint64_t* __restrict__ pos_off, uint32_t* out, uint64_t* vbits, uint64_t* pbits,
-                                                       unsigned long long* counters)
+                                                       unsigned long long* counters, uint64_t* in2, uint64_t* out2, uint64_t* br)
 {
     __shared__ uint32_t s_blk[SCAN_TILE][16];
     __shared__ uint64_t s_bid[SCAN_TILE];
@@ -388,6 +391,14 @@ __global__ void __launch_bounds__(SCAN_TILE) k_profile(Index ix, const uint64_t*
             }
             const unsigned long long vbal = __ballot((word >> 16) & 1u), pbal = __ballot((word >> 17) & 1u);
             if (lane == 0 && base + wave * 64u < npos) { vb[(base >> 6) + wave] = vbal; pb[(base >> 6) + wave] = pbal; }
+            if (HET) { /* an absent position has empty masks */
+                const int nin = popc4((word >> 12) & 15u), nout = popc4((word >> 8) & 15u);
+                const unsigned long long ibal = __ballot(nin == 2), obal = __ballot(nout == 2), bbal = __ballot(nin > 1 || nout > 1);
+                if (lane == 0 && base + wave * 64u < npos) {
+                    const size_t at = word_off[s] + (base >> 6) + wave;
+                    in2[at] = ibal; out2[at] = obal; br[at] = bbal;
+                }
+            }
             __syncthreads();
         }
     }
@@ -530,14 +541,41 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_mark_index(const uint32_t* __res
     if (on && at < cap) index[at] = (uint32_t)i;
 }
 
+/* The micro-assembly of the insertion observers (FindSmallInsertion.hpp:57-125, FindHeteroInsertion.hpp:80-116), by one wave: the first of the 20
+ * strings A, C, G, T, AA .. TT for which the first k windows of left + string + right are all solid, -1 when there is none.  lk / rk: the
+ * little-endian images of the two k-mers.  Two strings at a time: lanes 0-31 the windows 0 .. k-1 for string 2 * it, lanes 32-63 those of
+ * string 2 * it + 1 (k <= 32); a window is cut from the 128-bit image of the text and looked up by the path of k_query (abundance != 0).  The
+ * windows behind the k-th are not looked at, as in the reference, where nothing depends on them any more; the loop leaves at the first pair
+ * with a hit, the lower half before the upper.  The result is uniform in the wave */
+__device__ __forceinline__ int find_micro_assembly(const Index& ix, uint64_t lk, uint64_t rk, uint32_t lane, uint32_t& lines)
+{
+    const int k = ix.k;
+    const uint64_t mk = kmask(k), cmpl = 0xAAAAAAAAAAAAAAAAULL & mk;
+    const uint32_t half = lane >> 5, j = lane & 31u;
+    int found = -1;
+    for (uint32_t it = 0; it < 10u && found < 0; it++) {
+        const uint32_t si = 2u * it + half, n = si < 4u ? 1u : 2u;
+        /* codes of A, C, G, T in that order: 0, 1, 3, 2; the first inserted nucleotide lowest */
+        const uint32_t ins = si < 4u ? (0xB4u >> (2u * si)) & 3u : ((0xB4u >> (2u * ((si - 4u) >> 2))) & 3u) | (((0xB4u >> (2u * ((si - 4u) & 3u))) & 3u) << 2);
+        const unsigned __int128 text = (unsigned __int128)lk | ((unsigned __int128)ins << (2 * k)) | ((unsigned __int128)rk << (2 * (k + (int)n)));
+        bool solid = true;
+        if (j < (uint32_t)k) {
+            Kmer x;
+            x.r = ((uint64_t)(text >> (2u * j)) & mk) ^ cmpl;
+            x.f = revcomp(x.r, k);
+            solid = abundance(ix, x, lines) != 0;
+        }
+        const unsigned long long bal = __ballot(solid);
+        if ((uint32_t)bal == 0xFFFFFFFFu) found = (int)(2u * it);
+        else if ((uint32_t)(bal >> 32) == 0xFFFFFFFFu) found = (int)(2u * it + 1u);
+    }
+    return found;
+}
+
 /* The observers on one candidate gap, one wave each (four to a workgroup).  Gap of L positions from `start`, first solid position behind it
  * e = start + L, r = k - 1 - L: left k-mer at start - 1 (present: an anchor), right k-mer as written at e + r, which for r > 0 must lie in
  * the sequence and hold nucleotides only.  Lane 0 / lane 1 look up outdegree(left) / indegree(k-mer at e); every observer but the small
- * clean one wants both >= 1 (FindSmallInsertion.hpp:64 has no such test: kept).  The micro-assembly takes two of the 20 strings at a time:
- * lanes 0-31 the windows 0 .. k-1 of left + ins + right for string 2 * it, lanes 32-63 those of string 2 * it + 1 (k <= 32); a window is cut
- * from the 128-bit little-endian image of the text and looked up by the path of k_query (abundance != 0).  A string is called when its first
- * k windows are all solid -- the windows behind them are not looked at, as in the reference, where nothing depends on them any more -- and
- * the first string in the order A, C, G, T, AA .. TT wins: the loop leaves at the first pair with a hit, the lower half before the upper.
+ * clean one wants both >= 1 (FindSmallInsertion.hpp:64 has no such test: kept).  The micro-assembly is find_micro_assembly's.
  * res[c] = 0: no call; else 1 | kind << 1 | ins << 8.  counters[2..5] += homo clean, homo fuzzy, small clean, small fuzzy */
 enum { FIND_WAVES = 4 };
 __global__ void __launch_bounds__(FIND_WAVES * 64) k_find_assemble(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off, const uint32_t* __restrict__ len,
@@ -576,24 +614,7 @@ __global__ void __launch_bounds__(FIND_WAVES * 64) k_find_assemble(Index ix, con
         }
         const bool degrees = __ballot(!mine) == 0ull;
         if (r == 0 || degrees) {
-            const uint32_t half = lane >> 5, j = lane & 31u;
-            int found = -1;
-            for (uint32_t it = 0; it < 10u && found < 0; it++) {
-                const uint32_t si = 2u * it + half, n = si < 4u ? 1u : 2u;
-                /* codes of A, C, G, T in that order: 0, 1, 3, 2; the first inserted nucleotide lowest */
-                const uint32_t ins = si < 4u ? (0xB4u >> (2u * si)) & 3u : ((0xB4u >> (2u * ((si - 4u) >> 2))) & 3u) | (((0xB4u >> (2u * ((si - 4u) & 3u))) & 3u) << 2);
-                const unsigned __int128 text = (unsigned __int128)lk | ((unsigned __int128)ins << (2 * k)) | ((unsigned __int128)rk << (2 * (k + (int)n)));
-                bool solid = true;
-                if (j < (uint32_t)k) {
-                    Kmer x;
-                    x.r = ((uint64_t)(text >> (2u * j)) & mk) ^ cmpl;
-                    x.f = revcomp(x.r, k);
-                    solid = abundance(ix, x, lines) != 0;
-                }
-                const unsigned long long bal = __ballot(solid);
-                if ((uint32_t)bal == 0xFFFFFFFFu) found = (int)(2u * it);
-                else if ((uint32_t)(bal >> 32) == 0xFFFFFFFFu) found = (int)(2u * it + 1u);
-            }
+            const int found = find_micro_assembly(ix, lk, rk, lane, lines);
             if (found >= 0) out = 1u | (1u << 1) | ((uint32_t)found << 8);
             else if (degrees) out = 1u;
         }
@@ -614,6 +635,143 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_find_emit(const mtg_run* __restr
     const uint32_t e = g.start + g.length, r = (uint32_t)(k - 1) - g.length, kind = (o >> 1) & 1u;
     mtg_find_call q;
     q.seq = g.seq; q.pos = kind ? e - 1u : e - 1u + r; q.kind = kind; q.repeat = r; q.left = g.start - 1u; q.right = e + r; q.ins = o >> 8;
+    calls[j] = q;
+}
+
+/* ---- `find` for heterozygous insertions (include/mtg_fill.h: mtg_index_find_het_sequences; the rule and the word-level logic: mtg_find_het.h).
+ * k_profile<true> writes the planes.  k_het_count / k_profile_seq_scan / k_het_list: the candidate positions in scan order by the two counted
+ * passes of the runs (popcounts per plane word).  k_het_judge: one wave per candidate, the observer as if `recent` were 0.  k_het_chain: the
+ * head of every chain of raw sites accepts or drops its sites.  k_het_final: the other outcomes look back at the accepted sites; mark[c] = the
+ * candidate is a call.  k_mark_* list the calls in order, k_het_emit writes their records.
+ * counters: [0] candidates (a qualifying i exists), [1] raw sites, [2] refused by the branching filter, [3] suppressed by `recent`,
+ * [4] clean sites, [5] fuzzy sites, [6] insertions of 1-2 nt */
+__global__ void __launch_bounds__(RUNS_BLOCK) k_het_count(const uint64_t* __restrict__ vbits, const uint64_t* __restrict__ in2, const uint64_t* __restrict__ out2,
+                                                          const uint64_t* __restrict__ rep, const uint64_t* __restrict__ word_off, const uint32_t* __restrict__ len, size_t nseq,
+                                                          int k, int max_repeat, uint32_t* seq_cnt)
+{
+    __shared__ uint32_t s_w[RUNS_BLOCK / 64];
+    for (size_t s = blockIdx.x; s < nseq; s += gridDim.x) {
+        const uint32_t L = len[s], npos = L < (uint32_t)k ? 0u : L - (uint32_t)k + 1u, nw = run_words(npos);
+        const uint64_t o = word_off[s];
+        uint32_t mine = 0;
+        for (uint32_t w = threadIdx.x; w < nw; w += RUNS_BLOCK) mine += run_popc(het_cand_word(vbits + o, in2 + o, out2 + o, rep ? rep + o : nullptr, w, npos, k, max_repeat));
+        uint32_t excl;
+        const uint32_t total = runs_block_sum(mine, s_w, excl);
+        if (threadIdx.x == 0) seq_cnt[s] = total;
+    }
+}
+__global__ void __launch_bounds__(RUNS_BLOCK) k_het_list(const uint64_t* __restrict__ vbits, const uint64_t* __restrict__ in2, const uint64_t* __restrict__ out2,
+                                                         const uint64_t* __restrict__ rep, const uint64_t* __restrict__ word_off, const uint32_t* __restrict__ len, size_t nseq,
+                                                         int k, int max_repeat, const uint64_t* __restrict__ seq_before, HetEntry* e, uint64_t cap)
+{
+    __shared__ uint32_t s_w[RUNS_BLOCK / 64];
+    for (size_t s = blockIdx.x; s < nseq; s += gridDim.x) {
+        const uint32_t L = len[s], npos = L < (uint32_t)k ? 0u : L - (uint32_t)k + 1u, nw = run_words(npos);
+        const uint64_t o = word_off[s];
+        uint64_t before = seq_before[s];
+        for (uint32_t w0 = 0; w0 < nw; w0 += RUNS_BLOCK) {
+            const uint32_t w = w0 + threadIdx.x;
+            const uint64_t m = w < nw ? het_cand_word(vbits + o, in2 + o, out2 + o, rep ? rep + o : nullptr, w, npos, k, max_repeat) : 0ull;
+            uint32_t excl;
+            const uint32_t total = runs_block_sum(run_popc(m), s_w, excl);
+            uint64_t at = before + excl;
+            for (uint64_t x = m; x && at < cap; x &= x - 1ull, at++) { e[at].seq = (uint32_t)s; e[at].p = w * 64u + run_ctz(x); }
+            before += total;
+        }
+    }
+}
+__global__ void __launch_bounds__(FIND_WAVES * 64) k_het_judge(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off, const uint32_t* __restrict__ len,
+                                                               const uint64_t* __restrict__ bad, const uint64_t* __restrict__ vbits, const uint64_t* __restrict__ out2,
+                                                               const uint64_t* __restrict__ br, const uint64_t* __restrict__ rep, HetEntry* e, uint64_t n, int max_repeat,
+                                                               int branching_filter, unsigned long long* counters)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t c = (uint64_t)blockIdx.x * FIND_WAVES + (threadIdx.x >> 6);
+    if (c >= n) return; /* (uniform in the wave; the kernel has no workgroup barrier) */
+    const uint32_t s = e[c].seq, p = e[c].p;
+    const int k = ix.k;
+    const uint64_t mk = kmask(k), o = word_off[s];
+    const uint64_t *w = words + o, *vp = vbits + o, *op = out2 + o, *bp = br + o, *rp = rep ? rep + o : nullptr;
+    /* the first i whose history slot holds a k-mer of out-degree 2 with a suffix that is not repeated */
+    int64_t hq = -1;
+    bool ok = false;
+    if (lane <= (uint32_t)max_repeat) {
+        hq = het_history_pos(vp, (int64_t)p - k + (int64_t)lane);
+        ok = hq >= 0 && het_bit(op, (uint32_t)hq) && !(rp && het_bit(rp, (uint32_t)hq + 1u));
+    }
+    const unsigned long long bal = __ballot(ok);
+    uint32_t out = HET_NONE, i = 0, left = 0;
+    int found = -1;
+    if (bal) {
+        i = (uint32_t)__ffsll(bal) - 1u;
+        left = (uint32_t)__shfl((int)(uint32_t)hq, (int)i, 64);
+        const uint32_t L = len[s], right = p + i;
+        bool right_ok = (uint64_t)right + (uint32_t)k <= L;
+        if (right_ok && bad) { /* as k_profile: the k bits of the characters right .. right + k - 1 */
+            const uint64_t* bw = bad + o;
+            const uint32_t sh = right & 63u;
+            uint64_t m = bw[right >> 6] >> sh;
+            if (sh + (uint32_t)k > 64u) m |= bw[(right >> 6) + 1] << (64u - sh);
+            right_ok = (m & ((1ull << k) - 1ull)) == 0;
+        }
+        if (right_ok) {
+            uint32_t lines = 0;
+            found = find_micro_assembly(ix, le_kmer(w, left, mk), le_kmer(w, right, mk), lane, lines);
+            if (found >= 0) out = HET_INS;
+            else { /* the branching k-mers among the 100 history slots before the window */
+                uint32_t nb = 0;
+                for (uint32_t j0 = 1; j0 <= 100u; j0 += 64u) {
+                    const uint32_t j = j0 + lane;
+                    bool b = false;
+                    if (j <= 100u) {
+                        const int64_t h = het_history_pos(vp, (int64_t)p - k - (int64_t)j);
+                        b = h >= 0 && het_bit(bp, (uint32_t)h);
+                    }
+                    nb += (uint32_t)__popcll(__ballot(b));
+                }
+                out = (branching_filter < 0 || nb <= (uint32_t)branching_filter) ? HET_SITE : HET_FILTERED;
+            }
+        }
+    }
+    if (lane == 0) {
+        e[c].out = out; e[c].rep = i; e[c].left = left; e[c].ins = found >= 0 ? (uint32_t)found : 0u;
+        if (bal) atomicAdd(&counters[0], 1ull);
+        if (out == HET_SITE) atomicAdd(&counters[1], 1ull);
+    }
+}
+__global__ void __launch_bounds__(RUNS_BLOCK) k_het_chain(HetEntry* e, uint64_t n, const uint64_t* __restrict__ vbits, const uint64_t* __restrict__ word_off, int max_repeat)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    if (c >= n || e[c].out != HET_SITE) return;
+    if (het_is_head(e, vbits, word_off, c, (uint32_t)max_repeat)) het_walk_chain(e, n, vbits, word_off, c, (uint32_t)max_repeat);
+}
+__global__ void __launch_bounds__(RUNS_BLOCK) k_het_final(const HetEntry* __restrict__ e, uint64_t n, const uint64_t* __restrict__ vbits, const uint64_t* __restrict__ word_off,
+                                                          int max_repeat, uint32_t* mark, unsigned long long* counters)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    if (c >= n) return;
+    const uint32_t out = e[c].out;
+    uint32_t keep = 0;
+    if (out == HET_SITE) {
+        keep = e[c].state == HET_ACCEPTED;
+        atomicAdd(&counters[keep ? (e[c].rep ? 5 : 4) : 3], 1ull);
+    } else if (out != HET_NONE) {
+        const bool quiet = het_suppressed(e, vbits, word_off, c, (uint32_t)max_repeat);
+        keep = out == HET_INS && !quiet;
+        if (out == HET_INS) atomicAdd(&counters[quiet ? 3 : 6], 1ull);
+        else if (!quiet) atomicAdd(&counters[2], 1ull);
+    }
+    mark[c] = keep;
+}
+/* the records of the calls: call j is candidate sel[j] */
+__global__ void __launch_bounds__(RUNS_BLOCK) k_het_emit(const HetEntry* __restrict__ e, const uint32_t* __restrict__ sel, uint64_t n, mtg_find_call* calls)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const HetEntry h = e[sel[j]];
+    const bool site = h.out == HET_SITE;
+    mtg_find_call q;
+    q.seq = h.seq; q.pos = site ? h.p - 1u + h.rep : h.p - 1u; q.kind = site ? 2u : 3u; q.repeat = h.rep; q.left = h.left; q.right = h.p + h.rep; q.ins = site ? 0u : h.ins;
     calls[j] = q;
 }
 
@@ -919,7 +1077,7 @@ int profile_run(const mtg_index* idx, const uint64_t* words, size_t nwords, cons
     HIP_TRY(events.make(e0)); HIP_TRY(events.make(e1)); HIP_TRY(events.make(e2)); HIP_TRY(events.make(e3));
     const dim3 grid((unsigned)std::min<size_t>(nseq, 256 * 16));
     HIP_TRY(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(k_profile, grid, dim3(SCAN_TILE), 0, 0, idx->dev, pw, po, pl, nseq, pbad, ppo, pout, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt);
+    hipLaunchKernelGGL(k_profile<false>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, pw, po, pl, nseq, pbad, ppo, pout, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
     hipLaunchKernelGGL(k_profile_count<false>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_cnt.as<uint32_t>());
     hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + 4);
     HIP_TRY(hipEventRecord(e1, 0));
@@ -1013,7 +1171,7 @@ int find_homo_run(const mtg_index* idx, const uint64_t* words, size_t nwords, co
     float ms = 0, part = 0;
     /* 1. the planes, the gaps counted */
     HIP_TRY(hipEventRecord(ev[0], 0));
-    hipLaunchKernelGGL(k_profile, grid, dim3(SCAN_TILE), 0, 0, idx->dev, pw, po, pl, nseq, pbad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt);
+    hipLaunchKernelGGL(k_profile<false>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, pw, po, pl, nseq, pbad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
     hipLaunchKernelGGL(k_profile_count<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_cnt.as<uint32_t>());
     hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + 4);
     HIP_TRY(hipEventRecord(ev[1], 0));
@@ -1065,6 +1223,98 @@ int find_homo_run(const mtg_index* idx, const uint64_t* words, size_t nwords, co
     if (st) {
         st->n_positions = c[0]; st->n_gaps = c[8]; st->n_candidates = n_cand;
         st->n_homo_clean = c[10]; st->n_homo_fuzzy = c[11]; st->n_small_clean = c[12]; st->n_small_fuzzy = c[13];
+        st->kernel_ms = (double)ms;
+    }
+    return MTG_OK;
+}
+
+/* `find` for heterozygous insertions over packed sequences (mtg_index_find_het_sequences / _packed_device).  device_ptrs = 0: words / word_off /
+ * len / bad / rep are host arrays (bad and rep of nwords words each, rep may be null) and calls host memory; 1: all of them device memory
+ * (nwords unused, bad null).  Beyond the input: six planes of a bit per position and one HetEntry per candidate */
+int find_het_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, const uint64_t* rep,
+                 int max_repeat, int branching_filter, mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_het_stats* st)
+{
+    if (int rc = use_device_of(idx)) return rc;
+    if (!idx || !idx->dev.bloom.bits) { set_error("the index has no Bloom filter (MTG_BLOOM_BITS=0)"); return MTG_ERR_ARG; }
+    *n_calls = 0;
+    if (st) *st = mtg_find_het_stats{};
+    if (nseq == 0) return MTG_OK;
+    const int k = idx->dev.k;
+    if (max_repeat > k - 2) max_repeat = k - 2;
+    DevBuf d_w, d_o, d_l, d_bad, d_rep, d_v, d_p, d_in2, d_out2, d_br, d_cnt, d_before, d_c, d_e, d_mark, d_blk_cnt, d_blk_before, d_sel, d_calls;
+    const uint64_t *pw = words, *po = word_off, *pbad = bad, *prep = rep;
+    const uint32_t* pl = len;
+    if (!device_ptrs) {
+        HIP_TRY(d_w.alloc(nwords * 8)); HIP_TRY(d_o.alloc(nseq * 8)); HIP_TRY(d_l.alloc(nseq * 4));
+        HIP_TRY(hipMemcpy(d_w.p, words, nwords * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_o.p, word_off, nseq * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_l.p, len, nseq * 4, hipMemcpyHostToDevice));
+        pw = d_w.as<uint64_t>(); po = d_o.as<uint64_t>(); pl = d_l.as<uint32_t>();
+        if (bad) { HIP_TRY(d_bad.alloc(nwords * 8)); HIP_TRY(hipMemcpy(d_bad.p, bad, nwords * 8, hipMemcpyHostToDevice)); pbad = d_bad.as<uint64_t>(); }
+        if (rep) { HIP_TRY(d_rep.alloc(nwords * 8)); HIP_TRY(hipMemcpy(d_rep.p, rep, nwords * 8, hipMemcpyHostToDevice)); prep = d_rep.as<uint64_t>(); }
+    } else { /* as profile_run: how far the planes reach */
+        std::vector<uint64_t> ho(nseq);
+        std::vector<uint32_t> hl(nseq);
+        HIP_TRY(hipMemcpy(ho.data(), word_off, nseq * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hl.data(), len, nseq * 4, hipMemcpyDeviceToHost));
+        nwords = 0;
+        for (size_t s = 0; s < nseq; s++) nwords = std::max<size_t>(nwords, (size_t)ho[s] + hl[s] / 64 + 1);
+    }
+    HIP_TRY(d_v.alloc(nwords * 8)); HIP_TRY(d_p.alloc(nwords * 8)); HIP_TRY(d_in2.alloc(nwords * 8)); HIP_TRY(d_out2.alloc(nwords * 8)); HIP_TRY(d_br.alloc(nwords * 8));
+    HIP_TRY(d_cnt.alloc(nseq * 4)); HIP_TRY(d_before.alloc(nseq * 8));
+    HIP_TRY(d_c.alloc(128));
+    HIP_TRY(hipMemset(d_c.p, 0, 128));
+    unsigned long long* cnt = d_c.as<unsigned long long>(); /* [0..2] k_profile's counters, [4] candidates listed, [6] calls, [8..14] the counters of k_het_judge / k_het_final */
+    EventSet events;
+    hipEvent_t ev[4];
+    for (hipEvent_t& e : ev) HIP_TRY(events.make(e));
+    const dim3 grid((unsigned)std::min<size_t>(nseq, 256 * 16));
+    unsigned long long c[16];
+    float ms = 0, part = 0;
+    /* 1. the planes, the candidates counted */
+    HIP_TRY(hipEventRecord(ev[0], 0));
+    hipLaunchKernelGGL(k_profile<true>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, pw, po, pl, nseq, pbad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt,
+                       d_in2.as<uint64_t>(), d_out2.as<uint64_t>(), d_br.as<uint64_t>());
+    hipLaunchKernelGGL(k_het_count, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_in2.as<uint64_t>(), d_out2.as<uint64_t>(), prep, po, pl, nseq, k, max_repeat, d_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + 4);
+    HIP_TRY(hipEventRecord(ev[1], 0));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(c, d_c.p, 128, hipMemcpyDeviceToHost));
+    HIP_TRY(hipEventElapsedTime(&part, ev[0], ev[1])); ms += part;
+    const uint64_t n_cand = c[4];
+    if (n_cand > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 candidates"); return MTG_ERR_ARG; }
+    uint64_t total = 0;
+    if (n_cand) {
+        /* 2. the candidates listed and judged, the chains resolved, the calls listed in order and written */
+        HIP_TRY(d_e.alloc((size_t)n_cand * sizeof(HetEntry)));
+        HIP_TRY(hipMemset(d_e.p, 0, (size_t)n_cand * sizeof(HetEntry)));
+        HIP_TRY(d_mark.alloc((size_t)n_cand * 4));
+        const unsigned cb = (unsigned)((n_cand + RUNS_BLOCK - 1) / RUNS_BLOCK);
+        HIP_TRY(hipEventRecord(ev[2], 0));
+        hipLaunchKernelGGL(k_het_list, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_in2.as<uint64_t>(), d_out2.as<uint64_t>(), prep, po, pl, nseq, k, max_repeat, d_before.as<uint64_t>(),
+                           d_e.as<HetEntry>(), n_cand);
+        hipLaunchKernelGGL(k_het_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, pw, po, pl, pbad, d_v.as<uint64_t>(), d_out2.as<uint64_t>(),
+                           d_br.as<uint64_t>(), prep, d_e.as<HetEntry>(), n_cand, max_repeat, branching_filter, cnt + 8);
+        hipLaunchKernelGGL(k_het_chain, dim3(cb), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), n_cand, d_v.as<uint64_t>(), po, max_repeat);
+        hipLaunchKernelGGL(k_het_final, dim3(cb), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), n_cand, d_v.as<uint64_t>(), po, max_repeat, d_mark.as<uint32_t>(), cnt + 8);
+        if (int rc = mark_compact(d_mark.as<uint32_t>(), n_cand, d_blk_cnt, d_blk_before, cnt + 6, d_sel, cap, &total)) return rc;
+        const uint64_t keep = std::min<uint64_t>(total, cap);
+        mtg_find_call* pc = calls;
+        if (keep) {
+            if (!device_ptrs) { HIP_TRY(d_calls.alloc((size_t)keep * sizeof(mtg_find_call))); pc = d_calls.as<mtg_find_call>(); }
+            hipLaunchKernelGGL(k_het_emit, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), d_sel.as<uint32_t>(), keep, pc);
+        }
+        HIP_TRY(hipEventRecord(ev[3], 0));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventSynchronize(ev[3]));
+        if (keep && !device_ptrs) HIP_TRY(hipMemcpy(calls, pc, (size_t)keep * sizeof(mtg_find_call), hipMemcpyDeviceToHost));
+        HIP_TRY(hipEventElapsedTime(&part, ev[2], ev[3])); ms += part;
+        HIP_TRY(hipMemcpy(c, d_c.p, 128, hipMemcpyDeviceToHost));
+    }
+    *n_calls = (size_t)total;
+    if (st) {
+        st->n_positions = c[0]; st->n_candidates = c[8]; st->n_raw_sites = c[9]; st->n_filtered = c[10]; st->n_suppressed = c[11];
+        st->n_het_clean = c[12]; st->n_het_fuzzy = c[13]; st->n_het_small = c[14];
         st->kernel_ms = (double)ms;
     }
     return MTG_OK;

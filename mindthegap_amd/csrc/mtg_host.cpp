@@ -136,6 +136,12 @@ __attribute__((weak)) int find_homo_run(const mtg_index*, const uint64_t*, size_
     set_error("this build has no device code for find");
     return MTG_ERR_NO_DEVICE;
 }
+__attribute__((weak)) int find_het_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, const uint64_t*, int, int, mtg_find_call*, size_t,
+                                       size_t*, int, mtg_find_het_stats*)
+{
+    set_error("this build has no device code for find");
+    return MTG_ERR_NO_DEVICE;
+}
 
 /* ------------------------------------------------------------------------------------------------ index from reads */
 static inline bool nt_bad(unsigned char c) { return (c >> 3) & 1; } /* gatb: bit 3 of the ASCII code flags 'N' */
@@ -1932,6 +1938,35 @@ int mtg_index_find_homo_packed_device(const mtg_index* idx, const uint64_t* d_wo
     if (!idx || !n_calls || (nseq && (!d_words || !d_word_off || !d_len)) || (cap && !d_calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
     if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
     return mtgi::find_homo_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, d_calls, cap, n_calls, 1, st);
+}
+
+int mtg_index_find_het_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, const uint8_t* const* repeated, int max_repeat, int branching_filter, mtg_find_call* calls,
+                                 size_t cap, size_t* n_calls, mtg_find_het_stats* st)
+{
+    if (!idx || !n_calls || (nseq && !seqs) || (cap && !calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
+    const int k = idx->dev.k;
+    std::vector<uint64_t> off, pos_off, words, bad, rep;
+    std::vector<uint32_t> len;
+    uint64_t npos = 0;
+    if (!pack_with_bad_bits(seqs, nseq, k, nullptr, off, len, pos_off, npos, words, bad)) return MTG_ERR_ARG;
+    if (repeated) { /* the repeat plane: one bit per (k-1)-mer position, at the sequence's word offset */
+        rep.assign(words.size(), 0);
+        for (size_t s = 0; s < nseq; s++) {
+            if (len[s] < (uint32_t)k) continue;
+            if (!repeated[s]) { mtgi::set_error("sequence %zu: null repeat flags", s); return MTG_ERR_ARG; }
+            for (uint32_t q = 0; q < len[s] - (uint32_t)k + 2u; q++)
+                if (repeated[s][q]) rep[off[s] + (q >> 6)] |= 1ull << (q & 63);
+        }
+    }
+    return mtgi::find_het_run(idx, words.data(), words.size(), off.data(), len.data(), nseq, bad.data(), repeated ? rep.data() : nullptr, max_repeat, branching_filter, calls, cap, n_calls, 0, st);
+}
+int mtg_index_find_het_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, const uint64_t* d_repeat_bits,
+                                     int max_repeat, int branching_filter, mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_het_stats* st)
+{
+    if (!idx || !n_calls || (nseq && (!d_words || !d_word_off || !d_len)) || (cap && !d_calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
+    return mtgi::find_het_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, d_repeat_bits, max_repeat, branching_filter, d_calls, cap, n_calls, 1, st);
 }
 
 int mtg_nw_matches(const char* const* a, const char* const* b, size_t n, uint32_t* matches)

@@ -102,7 +102,13 @@ class FindStats(C.Structure):
                 ("n_small_clean", C.c_uint64), ("n_small_fuzzy", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
-# a call of `find` for homozygous insertions (mtg_find_call): kind 0 = insertion site, 1 = insertion of 1-2 nt; ins indexes FIND_INSERTIONS
+class FindHetStats(C.Structure):
+    _fields_ = [("n_positions", C.c_uint64), ("n_candidates", C.c_uint64), ("n_raw_sites", C.c_uint64), ("n_filtered", C.c_uint64), ("n_suppressed", C.c_uint64),
+                ("n_het_clean", C.c_uint64), ("n_het_fuzzy", C.c_uint64), ("n_het_small", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+# a call of `find` (mtg_find_call): kind 0 = homozygous insertion site, 1 = homozygous insertion of 1-2 nt, 2 = heterozygous site,
+# 3 = heterozygous insertion of 1-2 nt; ins indexes FIND_INSERTIONS
 CALL_DTYPE = np.dtype([("seq", np.uint32), ("pos", np.uint32), ("kind", np.uint32), ("repeat", np.uint32), ("left", np.uint32), ("right", np.uint32), ("ins", np.uint32)])
 FIND_INSERTIONS = ("A", "C", "G", "T", "AA", "AC", "AG", "AT", "CA", "CC", "CG", "CT", "GA", "GC", "GG", "GT", "TA", "TC", "TG", "TT")
 
@@ -214,6 +220,9 @@ def _bind(lib):
     lib.mtg_profile_main.argtypes = [C.c_int, P(C.c_char_p)]
     lib.mtg_index_find_homo_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindStats)]
     lib.mtg_index_find_homo_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindStats)]
+    lib.mtg_index_find_het_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindHetStats)]
+    lib.mtg_index_find_het_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t),
+                                                     P(FindHetStats)]
     lib.mtg_find_main.argtypes = [C.c_int, P(C.c_char_p)]
     lib.mtg_default_params.argtypes = [P(Params)]
     lib.mtg_default_params.restype = None
@@ -558,6 +567,37 @@ class Index:
         total, st = C.c_size_t(), FindStats()
         _check(self.lib.mtg_index_find_homo_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap, C.byref(total), C.byref(st)))
         return total.value, {f[0]: getattr(st, f[0]) for f in FindStats._fields_}
+
+    def find_het_sequences(self, seqs, repeated=None, max_repeat=5, branching_filter=15, cap=None):
+        """`find` for heterozygous insertions: the sites (kind 2) and the insertions of 1-2 nt (kind 3) of seqs against the graph; returns (calls
+        as a CALL_DTYPE array in the order of the scan, stats dict).  repeated: per sequence a uint8 array of len - k + 2 flags, one per
+        (k-1)-mer position (what scan_sequences of an index of k - 1 returns), or None: nothing is repeated.  branching_filter < 0: no filter.
+        cap as in find_homo_sequences."""
+        n = len(seqs)
+        arr = (C.c_char_p * n)(*[s.encode() for s in seqs])
+        rep = keep = None
+        if repeated is not None:
+            keep = [np.ascontiguousarray(r, dtype=np.uint8) for r in repeated]
+            rep = (C.c_void_p * n)(*[r.ctypes.data if r.size else None for r in keep])
+        room = 1024 if cap is None else int(cap)
+        while True:
+            calls = np.zeros(room, dtype=CALL_DTYPE)
+            total, st = C.c_size_t(), FindHetStats()
+            _check(self.lib.mtg_index_find_het_sequences(self.h, arr, n, rep, max_repeat, branching_filter, calls.ctypes.data if room else None, room, C.byref(total), C.byref(st)))
+            if cap is not None or total.value <= room:
+                break
+            room = total.value
+        stats = {f[0]: getattr(st, f[0]) for f in FindHetStats._fields_}
+        stats["n_calls"] = total.value
+        return calls[:min(total.value, room)], stats
+
+    def find_het_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, repeat_bits_ptr, max_repeat, branching_filter, calls_ptr, cap):
+        """the same on packed sequences in device memory (pointers as integers; repeat_bits_ptr: the repeat plane in the layout of
+        scan_packed_device's output for an index of k - 1, or None; calls_ptr: device array of cap mtg_find_call); returns (total calls, stats dict)"""
+        total, st = C.c_size_t(), FindHetStats()
+        _check(self.lib.mtg_index_find_het_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, repeat_bits_ptr, max_repeat, branching_filter, calls_ptr, cap, C.byref(total),
+                                                         C.byref(st)))
+        return total.value, {f[0]: getattr(st, f[0]) for f in FindHetStats._fields_}
 
     def stage_a(self, sources, targets, params=None):
         """Contigs of every gap (gatb IterativeExtensions::construct_linear_seqs, src/Filler.cpp:884)."""
