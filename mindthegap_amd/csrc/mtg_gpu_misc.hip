@@ -3,7 +3,8 @@
  *
  *   k_query                          : batched contains / queryAbundance / successors / predecessors
  *   k_scan                           : rolling 2-bit k-mer + minimizer-blocked Bloom probe along packed sequences, blocks staged in LDS
- *   k_profile, k_profile_*           : the scan's sibling that also answers abundance and degrees per position, and the runs of absent k-mers
+ *   k_profile, k_profile_*           : the scan's sibling (the same tile stage, scan_tile_stage) that also answers abundance and degrees per
+ *                                      position, and the runs of absent k-mers
  *   k_find_*, k_mark_*               : `find` for homozygous insertions: the scan's gaps, their candidates compacted in order, one wave per
  *                                      candidate for the degree tests and the micro-assembly of 1-2 nt, the calls compacted in order
  *   k_nw                             : Needleman-Wunsch match counts for the de-duplication of multi-path solutions, one wave per pair
@@ -211,20 +212,69 @@ __global__ void __launch_bounds__(64) k_nw(const uint8_t* __restrict__ text, con
 }
 
 /* membership scan along packed sequences: rolling k-mer per position, minimizer-blocked Bloom with the blocks of a 256-position tile
- * staged in LDS by coalesced 64-byte reads, optional exact confirmation in the ABND table.
- * counters: [0] k-mers, [1] Bloom positives, [2] confirmed, [3] blocks staged */
+ * staged in LDS by coalesced 64-byte reads, optional exact confirmation in the ABND table */
 enum { SCAN_TILE = 256 };
-__global__ void __launch_bounds__(SCAN_TILE) k_scan(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off,
-                                                    const uint32_t* __restrict__ len, size_t nseq, int mode, uint64_t* out_bits, unsigned long long* counters)
+struct ScanTile { /* a tile's LDS */
+    uint32_t blk[SCAN_TILE][16];     /* the staged Bloom blocks, one per run of positions with the same block */
+    uint64_t bid[SCAN_TILE];         /* the block of each position */
+    uint64_t slot_bid[SCAN_TILE];    /* the block of each slot of blk */
+    uint32_t wave_cnt[SCAN_TILE / 64];
+    uint64_t mh[SCAN_TILE + 32];     /* hashes of the tile's m-mers */
+};
+/* The front end of a tile of k_scan and k_profile, called once per tile by every thread of the workgroup (all its barriers are in here):
+ * positions base .. base + 255 of a sequence of npos positions with the packed words w.  x = the thread's k-mer at base + tid (zero when
+ * that position is outside the sequence), T.blk[slot] = the Bloom block of that k-mer (inside the sequence), total = blocks staged.
+ * The caller puts a barrier between its last read of T.blk and the next tile */
+__device__ __forceinline__ void scan_tile_stage(const Index& ix, ScanTile& T, const uint64_t* __restrict__ w, uint32_t base, uint32_t npos, Kmer& x, uint32_t& slot, uint32_t& total)
 {
-    __shared__ uint32_t s_blk[SCAN_TILE][16];
-    __shared__ uint64_t s_bid[SCAN_TILE];
-    __shared__ uint64_t s_slot_bid[SCAN_TILE];
-    __shared__ uint32_t s_wave_cnt[SCAN_TILE / 64];
-    __shared__ uint64_t s_mh[SCAN_TILE + 32]; /* hashes of the tile's m-mers */
     const int k = ix.k, mm = ix.bloom.mm;
     const uint32_t span = (uint32_t)(k - mm);
     const uint64_t mk = kmask(k), mmask = kmask(mm);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, p = base + tid;
+    const bool in_seq = p < npos;
+    /* the minimizer of a k-mer is the smallest hash among its k - m + 1 m-mers and neighbouring k-mers share all but one of them: the
+     * tile's m-mers are hashed once (256 + k - m of them, one or two per thread) and a k-mer takes the minimum over its window in LDS
+     * (rounds 1-4: bloom_block hashed fifteen m-mers per k-mer -- the kernel was bound by those multiplications, not by its reads) */
+    const uint32_t tile_k = npos - base < (uint32_t)SCAN_TILE ? npos - base : (uint32_t)SCAN_TILE, tile_m = tile_k + span;
+    for (uint32_t t = tid; t < tile_m; t += SCAN_TILE) {
+        const uint32_t j = base + t, sh = 2u * (j & 31u);
+        uint64_t v = w[j >> 5] >> sh;
+        if ((j & 31u) + (uint32_t)mm > 32u) v |= w[(j >> 5) + 1] << (64u - sh);
+        T.mh[t] = bloom_mmer_hash(v & mmask, mm);
+    }
+    __syncthreads();
+    x.f = x.r = 0;
+    uint64_t b = ~0ull;
+    if (in_seq) {
+        x.r = le_kmer(w, p, mk) ^ (0xAAAAAAAAAAAAAAAAULL & mk);
+        x.f = revcomp(x.r, k);
+        uint64_t best = ~0ull;
+        for (uint32_t t = 0; t <= span; t++) { const uint64_t h = T.mh[tid + t]; best = h < best ? h : best; }
+        b = bloom_block_of_min(ix.bloom, best);
+    }
+    T.bid[tid] = b;
+    __syncthreads();
+    const bool leader = in_seq && (tid == 0 || T.bid[tid - 1] != b);
+    const unsigned long long bal = __ballot(leader);
+    const uint32_t prefix = (uint32_t)__popcll(bal & ((lane == 63u) ? ~0ull : ((2ull << lane) - 1ull)));
+    if (lane == 0) T.wave_cnt[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t woff = 0;
+    total = 0;
+    for (uint32_t i = 0; i < SCAN_TILE / 64; i++) { if (i < wave) woff += T.wave_cnt[i]; total += T.wave_cnt[i]; }
+    slot = woff + prefix - 1u; /* a follower at the start of a wave continues the last block of the previous wave */
+    if (leader) T.slot_bid[slot] = b;
+    __syncthreads();
+    for (uint32_t i = tid; i < total * 16u; i += SCAN_TILE) T.blk[i >> 4][i & 15u] = ix.bloom.bits[T.slot_bid[i >> 4] * 16u + (i & 15u)];
+    __syncthreads();
+}
+
+enum { SCAN_KMERS, SCAN_BLOOM_POSITIVE, SCAN_CONFIRMED, SCAN_BLOCKS_STAGED, SCAN_COUNTERS }; /* k_scan's counters */
+__global__ void __launch_bounds__(SCAN_TILE) k_scan(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off,
+                                                    const uint32_t* __restrict__ len, size_t nseq, int mode, uint64_t* out_bits, unsigned long long* counters)
+{
+    __shared__ ScanTile T;
+    const int k = ix.k;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     unsigned long long n_k = 0, n_pos = 0, n_conf = 0, n_staged = 0;
     for (size_t s = blockIdx.x; s < nseq; s += gridDim.x) {
@@ -234,47 +284,14 @@ __global__ void __launch_bounds__(SCAN_TILE) k_scan(Index ix, const uint64_t* __
         uint64_t* ob = out_bits + word_off[s];
         const uint32_t npos = L - (uint32_t)k + 1;
         for (uint32_t base = 0; base < npos; base += SCAN_TILE) {
-            const uint32_t p = base + tid;
-            const bool valid = p < npos;
-            /* the minimizer of a k-mer is the smallest hash among its k - m + 1 m-mers and neighbouring k-mers share all but one of them: the
-             * tile's m-mers are hashed once (256 + k - m of them, one or two per thread) and a k-mer takes the minimum over its window in LDS
-             * (rounds 1-4: bloom_block hashed fifteen m-mers per k-mer -- the kernel was bound by those multiplications, not by its reads) */
-            const uint32_t tile_k = npos - base < (uint32_t)SCAN_TILE ? npos - base : (uint32_t)SCAN_TILE, tile_m = tile_k + span;
-            for (uint32_t t = tid; t < tile_m; t += SCAN_TILE) {
-                const uint32_t j = base + t, sh = 2u * (j & 31u);
-                uint64_t v = w[j >> 5] >> sh;
-                if ((j & 31u) + (uint32_t)mm > 32u) v |= w[(j >> 5) + 1] << (64u - sh);
-                s_mh[t] = bloom_mmer_hash(v & mmask, mm);
-            }
-            __syncthreads();
+            const bool valid = base + tid < npos;
             Kmer x;
-            x.f = x.r = 0;
-            uint64_t b = ~0ull;
-            if (valid) {
-                x.r = le_kmer(w, p, mk) ^ (0xAAAAAAAAAAAAAAAAULL & mk);
-                x.f = revcomp(x.r, k);
-                uint64_t best = ~0ull;
-                for (uint32_t t = 0; t <= span; t++) { const uint64_t h = s_mh[tid + t]; best = h < best ? h : best; }
-                b = bloom_block_of_min(ix.bloom, best);
-            }
-            s_bid[tid] = b;
-            __syncthreads();
-            const bool leader = valid && (tid == 0 || s_bid[tid - 1] != b);
-            const unsigned long long bal = __ballot(leader);
-            const uint32_t prefix = (uint32_t)__popcll(bal & ((lane == 63u) ? ~0ull : ((2ull << lane) - 1ull)));
-            if (lane == 0) s_wave_cnt[wave] = (uint32_t)__popcll(bal);
-            __syncthreads();
-            uint32_t woff = 0, total = 0;
-            for (uint32_t i = 0; i < SCAN_TILE / 64; i++) { if (i < wave) woff += s_wave_cnt[i]; total += s_wave_cnt[i]; }
-            const uint32_t slot = woff + prefix - 1u; /* a follower at the start of a wave continues the last block of the previous wave */
-            if (leader) s_slot_bid[slot] = b;
-            __syncthreads();
-            for (uint32_t i = tid; i < total * 16u; i += SCAN_TILE) s_blk[i >> 4][i & 15u] = ix.bloom.bits[s_slot_bid[i >> 4] * 16u + (i & 15u)];
-            __syncthreads();
+            uint32_t slot, total;
+            scan_tile_stage(ix, T, w, base, npos, x, slot, total);
             bool res = false;
             if (valid) {
                 const uint64_t c = canon(x);
-                res = bloom_test_block(s_blk[slot], bloom_bits(c));
+                res = bloom_test_block(T.blk[slot], bloom_bits(c));
                 n_k++;
                 n_pos += res;
                 if (res && mode == 1) {
@@ -290,34 +307,37 @@ __global__ void __launch_bounds__(SCAN_TILE) k_scan(Index ix, const uint64_t* __
         }
     }
     /* per-workgroup totals */
-    __shared__ unsigned long long s_tot[4];
-    if (tid < 4) s_tot[tid] = 0;
+    __shared__ unsigned long long s_tot[SCAN_COUNTERS];
+    if (tid < SCAN_COUNTERS) s_tot[tid] = 0;
     __syncthreads();
-    atomicAdd(&s_tot[0], n_k); atomicAdd(&s_tot[1], n_pos); atomicAdd(&s_tot[2], n_conf); atomicAdd(&s_tot[3], n_staged);
+    atomicAdd(&s_tot[SCAN_KMERS], n_k); atomicAdd(&s_tot[SCAN_BLOOM_POSITIVE], n_pos); atomicAdd(&s_tot[SCAN_CONFIRMED], n_conf); atomicAdd(&s_tot[SCAN_BLOCKS_STAGED], n_staged);
     __syncthreads();
-    if (tid < 4 && s_tot[tid]) atomicAdd(&counters[tid], s_tot[tid]);
+    if (tid < SCAN_COUNTERS && s_tot[tid]) atomicAdd(&counters[tid], s_tot[tid]);
 }
 
-/* profile along packed sequences: k_scan's tile (the tile's m-mers hashed once in LDS, Bloom blocks staged by coalesced reads, pre-filter,
- * exact confirmation), and for the confirmed positions the abundance and the neighbour masks of k_query, packed into one word per position
- * (include/mtg_fill.h).  bad = one bit per NUCLEOTIDE that is no nucleotide (bit i % 64 of bad[word_off[s] + i / 64]; nullptr: none): a k-mer
- * that covers one is invalid.  The valid and the present plane (bit layout of k_scan's output) go to vbits / pbits for k_profile_count /
- * k_profile_write.  counters: [0] positions, [1] valid, [2] present.  HET: three more planes for `find` for heterozygous insertions
- * (mtg_find_het.h): in2 / out2 = present with in- / out-degree 2, br = present with a degree above 1; nothing else differs */
+/* The counter block of profile_run / find_homo_run / find_het_run: 64-bit slots zeroed by the run, named here for its kernels and for the
+ * host's read-back alike.  Every block begins with k_profile's three; a total and a longest run are neighbours (k_profile_seq_scan writes
+ * tot[0], k_profile_finish tot[1]) */
+enum { CNT_POSITIONS, CNT_VALID, CNT_PRESENT, CNT_PROFILE };
+enum { CNT_RUNS = 4, CNT_RUNS_LONGEST, CNT_PROFILE_SLOTS = 8 };
+enum { CNT_GAPS = 4, CNT_GAPS_LONGEST, CNT_HOMO_CANDIDATES, CNT_HOMO_CALLS, CNT_GAPS_SEEN, CNT_HOMO_CLEAN = 10, CNT_HOMO_FUZZY, CNT_SMALL_CLEAN, CNT_SMALL_FUZZY, CNT_HOMO_SLOTS = 16 };
+enum { CNT_HET_LISTED = 4, CNT_HET_CALLS = 6, CNT_HET_CANDIDATES = 8, CNT_HET_RAW_SITES, CNT_HET_FILTERED, CNT_HET_SUPPRESSED, CNT_HET_CLEAN, CNT_HET_FUZZY, CNT_HET_SMALL, CNT_HET_SLOTS = 16 };
+
+/* profile along packed sequences: the tile of k_scan (scan_tile_stage: the tile's m-mers hashed once in LDS, Bloom blocks staged by coalesced
+ * reads; then pre-filter, exact confirmation), and for the confirmed positions the abundance and the neighbour masks of k_query, packed into one
+ * word per position (include/mtg_fill.h).  bad = one bit per NUCLEOTIDE that is no nucleotide (bit i % 64 of bad[word_off[s] + i / 64];
+ * nullptr: none): a k-mer that covers one is invalid.  The valid and the present plane (bit layout of k_scan's output) go to vbits / pbits for
+ * k_profile_count / k_profile_write.  HET: three more planes for `find` for heterozygous insertions (mtg_find_het.h): in2 / out2 = present
+ * with in- / out-degree 2, br = present with a degree above 1; nothing else differs */
 template <bool HET>
 __global__ void __launch_bounds__(SCAN_TILE) k_profile(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off,
                                                        const uint32_t* __restrict__ len, size_t nseq, const uint64_t* __restrict__ bad,
                                                        const uint64_t* __restrict__ pos_off, uint32_t* out, uint64_t* vbits, uint64_t* pbits,
                                                        unsigned long long* counters, uint64_t* in2, uint64_t* out2, uint64_t* br)
 {
-    __shared__ uint32_t s_blk[SCAN_TILE][16];
-    __shared__ uint64_t s_bid[SCAN_TILE];
-    __shared__ uint64_t s_slot_bid[SCAN_TILE];
-    __shared__ uint32_t s_wave_cnt[SCAN_TILE / 64];
-    __shared__ uint64_t s_mh[SCAN_TILE + 32]; /* hashes of the tile's m-mers */
-    const int k = ix.k, mm = ix.bloom.mm;
-    const uint32_t span = (uint32_t)(k - mm);
-    const uint64_t mk = kmask(k), mk1 = kmask(k - 1), mmask = kmask(mm);
+    __shared__ ScanTile T;
+    const int k = ix.k;
+    const uint64_t mk1 = kmask(k - 1);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     unsigned long long n_k = 0, n_valid = 0, n_present = 0;
     for (size_t s = blockIdx.x; s < nseq; s += gridDim.x) {
@@ -332,52 +352,17 @@ __global__ void __launch_bounds__(SCAN_TILE) k_profile(Index ix, const uint64_t*
         for (uint32_t base = 0; base < npos; base += SCAN_TILE) {
             const uint32_t p = base + tid;
             const bool in_seq = p < npos;
-            const uint32_t tile_k = npos - base < (uint32_t)SCAN_TILE ? npos - base : (uint32_t)SCAN_TILE, tile_m = tile_k + span;
-            for (uint32_t t = tid; t < tile_m; t += SCAN_TILE) {
-                const uint32_t j = base + t, sh = 2u * (j & 31u);
-                uint64_t v = w[j >> 5] >> sh;
-                if ((j & 31u) + (uint32_t)mm > 32u) v |= w[(j >> 5) + 1] << (64u - sh);
-                s_mh[t] = bloom_mmer_hash(v & mmask, mm);
-            }
-            __syncthreads();
             Kmer x;
-            x.f = x.r = 0;
-            uint64_t b = ~0ull;
-            bool ok = in_seq;
-            if (in_seq) {
-                x.r = le_kmer(w, p, mk) ^ (0xAAAAAAAAAAAAAAAAULL & mk);
-                x.f = revcomp(x.r, k);
-                uint64_t best = ~0ull;
-                for (uint32_t t = 0; t <= span; t++) { const uint64_t h = s_mh[tid + t]; best = h < best ? h : best; }
-                b = bloom_block_of_min(ix.bloom, best);
-                if (bw) { /* the k bits of the characters p .. p + k - 1 (k <= 32: at most two words) */
-                    const uint32_t sh = p & 63u;
-                    uint64_t m = bw[p >> 6] >> sh;
-                    if (sh + (uint32_t)k > 64u) m |= bw[(p >> 6) + 1] << (64u - sh);
-                    ok = (m & ((1ull << k) - 1ull)) == 0;
-                }
-            }
-            s_bid[tid] = b;
-            __syncthreads();
-            const bool leader = in_seq && (tid == 0 || s_bid[tid - 1] != b);
-            const unsigned long long bal = __ballot(leader);
-            const uint32_t prefix = (uint32_t)__popcll(bal & ((lane == 63u) ? ~0ull : ((2ull << lane) - 1ull)));
-            if (lane == 0) s_wave_cnt[wave] = (uint32_t)__popcll(bal);
-            __syncthreads();
-            uint32_t woff = 0, total = 0;
-            for (uint32_t i = 0; i < SCAN_TILE / 64; i++) { if (i < wave) woff += s_wave_cnt[i]; total += s_wave_cnt[i]; }
-            const uint32_t slot = woff + prefix - 1u; /* a follower at the start of a wave continues the last block of the previous wave */
-            if (leader) s_slot_bid[slot] = b;
-            __syncthreads();
-            for (uint32_t i = tid; i < total * 16u; i += SCAN_TILE) s_blk[i >> 4][i & 15u] = ix.bloom.bits[s_slot_bid[i >> 4] * 16u + (i & 15u)];
-            __syncthreads();
+            uint32_t slot, total;
+            scan_tile_stage(ix, T, w, base, npos, x, slot, total);
             uint32_t word = 0;
             if (in_seq) {
+                const bool ok = !(bw && covers_bad(bw, p, k));
                 n_k++;
                 n_valid += ok;
                 if (ok) {
                     word = 1u << 16;
-                    if (bloom_test_block(s_blk[slot], bloom_bits(canon(x)))) {
+                    if (bloom_test_block(T.blk[slot], bloom_bits(canon(x)))) {
                         uint32_t lines = 0;
                         const uint32_t a = abundance(ix, x, lines);
                         if (a) {
@@ -402,12 +387,12 @@ __global__ void __launch_bounds__(SCAN_TILE) k_profile(Index ix, const uint64_t*
             __syncthreads();
         }
     }
-    __shared__ unsigned long long s_tot[3];
-    if (tid < 3) s_tot[tid] = 0;
+    __shared__ unsigned long long s_tot[CNT_PROFILE];
+    if (tid < CNT_PROFILE) s_tot[tid] = 0;
     __syncthreads();
-    atomicAdd(&s_tot[0], n_k); atomicAdd(&s_tot[1], n_valid); atomicAdd(&s_tot[2], n_present);
+    atomicAdd(&s_tot[CNT_POSITIONS], n_k); atomicAdd(&s_tot[CNT_VALID], n_valid); atomicAdd(&s_tot[CNT_PRESENT], n_present);
     __syncthreads();
-    if (tid < 3 && s_tot[tid]) atomicAdd(&counters[tid], s_tot[tid]);
+    if (tid < CNT_PROFILE && s_tot[tid]) atomicAdd(&counters[tid], s_tot[tid]);
 }
 
 /* the runs of absent k-mers from the two planes (mtg_profile_runs.h), in ascending (seq, start) order by two counted passes:
@@ -507,7 +492,7 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_profile_finish(mtg_run* runs, ui
 
 /* ---- `find` for homozygous insertions (include/mtg_fill.h: mtg_index_find_homo_sequences).  The gaps of the scan come from
  * k_profile_count<true> / k_profile_write<true> as mtg_run records (flags: mtg_find_gaps.h).
- * k_find_mark: one thread per gap, the length test alone -- mark[i] = the gap is a candidate; counters[0] += gaps the observers see.
+ * k_find_mark: one thread per gap, the length test alone -- mark[i] = the gap is a candidate; CNT_GAPS_SEEN += gaps the observers see.
  * k_mark_count / k_profile_seq_scan / k_mark_index: the indices of the non-zero marks in ascending order (counts per workgroup, their
  * exclusive prefix sums, then every workgroup numbers its own); used for the candidates and, after k_find_assemble, for the calls. */
 __global__ void __launch_bounds__(RUNS_BLOCK) k_find_mark(const mtg_run* __restrict__ gaps, uint64_t n, int k, int max_repeat, uint32_t* mark, unsigned long long* counters)
@@ -520,7 +505,7 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_find_mark(const mtg_run* __restr
         mark[i] = gap_is_candidate(g.length, g.flags, k, max_repeat) ? 1u : 0u;
     }
     const unsigned long long bal = __ballot(seen);
-    if ((threadIdx.x & 63u) == 0 && bal) atomicAdd(&counters[0], (unsigned long long)__popcll(bal));
+    if ((threadIdx.x & 63u) == 0 && bal) atomicAdd(&counters[CNT_GAPS_SEEN], (unsigned long long)__popcll(bal));
 }
 __global__ void __launch_bounds__(RUNS_BLOCK) k_mark_count(const uint32_t* __restrict__ mark, uint64_t n, uint32_t* blk_cnt)
 {
@@ -576,7 +561,7 @@ __device__ __forceinline__ int find_micro_assembly(const Index& ix, uint64_t lk,
  * e = start + L, r = k - 1 - L: left k-mer at start - 1 (present: an anchor), right k-mer as written at e + r, which for r > 0 must lie in
  * the sequence and hold nucleotides only.  Lane 0 / lane 1 look up outdegree(left) / indegree(k-mer at e); every observer but the small
  * clean one wants both >= 1 (FindSmallInsertion.hpp:64 has no such test: kept).  The micro-assembly is find_micro_assembly's.
- * res[c] = 0: no call; else 1 | kind << 1 | ins << 8.  counters[2..5] += homo clean, homo fuzzy, small clean, small fuzzy */
+ * res[c] = 0: no call; else 1 | kind << 1 | ins << 8.  One of CNT_HOMO_CLEAN .. CNT_SMALL_FUZZY += 1 per call */
 enum { FIND_WAVES = 4 };
 __global__ void __launch_bounds__(FIND_WAVES * 64) k_find_assemble(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off, const uint32_t* __restrict__ len,
                                                                    const uint64_t* __restrict__ bad, const mtg_run* __restrict__ gaps, const uint32_t* __restrict__ cand, uint64_t ncand,
@@ -593,13 +578,7 @@ __global__ void __launch_bounds__(FIND_WAVES * 64) k_find_assemble(Index ix, con
     bool right_ok = true; /* r = 0: the k-mer at e, present */
     if (r) {
         right_ok = (uint64_t)rp + (uint32_t)k <= L;
-        if (right_ok && bad) { /* as k_profile: the k bits of the characters rp .. rp + k - 1 */
-            const uint64_t* bw = bad + word_off[g.seq];
-            const uint32_t sh = rp & 63u;
-            uint64_t m = bw[rp >> 6] >> sh;
-            if (sh + (uint32_t)k > 64u) m |= bw[(rp >> 6) + 1] << (64u - sh);
-            right_ok = (m & ((1ull << k) - 1ull)) == 0;
-        }
+        if (right_ok && bad) right_ok = !covers_bad(bad + word_off[g.seq], rp, k);
     }
     uint32_t out = 0;
     if (right_ok) {
@@ -621,7 +600,7 @@ __global__ void __launch_bounds__(FIND_WAVES * 64) k_find_assemble(Index ix, con
     }
     if (lane == 0) {
         res[c] = out;
-        if (out) atomicAdd(&counters[2 + ((out >> 1) & 1u) * 2u + (r ? 1u : 0u)], 1ull);
+        if (out) atomicAdd(&counters[((out >> 1) & 1u) ? (r ? CNT_SMALL_FUZZY : CNT_SMALL_CLEAN) : (r ? CNT_HOMO_FUZZY : CNT_HOMO_CLEAN)], 1ull);
     }
 }
 /* the records of the calls: call j is candidate sel[j] */
@@ -643,8 +622,8 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_find_emit(const mtg_run* __restr
  * passes of the runs (popcounts per plane word).  k_het_judge: one wave per candidate, the observer as if `recent` were 0.  k_het_chain: the
  * head of every chain of raw sites accepts or drops its sites.  k_het_final: the other outcomes look back at the accepted sites; mark[c] = the
  * candidate is a call.  k_mark_* list the calls in order, k_het_emit writes their records.
- * counters: [0] candidates (a qualifying i exists), [1] raw sites, [2] refused by the branching filter, [3] suppressed by `recent`,
- * [4] clean sites, [5] fuzzy sites, [6] insertions of 1-2 nt */
+ * counters (CNT_HET_*): candidates (a qualifying i exists), raw sites, refused by the branching filter, suppressed by `recent`, clean sites,
+ * fuzzy sites, insertions of 1-2 nt */
 __global__ void __launch_bounds__(RUNS_BLOCK) k_het_count(const uint64_t* __restrict__ vbits, const uint64_t* __restrict__ in2, const uint64_t* __restrict__ out2,
                                                           const uint64_t* __restrict__ rep, const uint64_t* __restrict__ word_off, const uint32_t* __restrict__ len, size_t nseq,
                                                           int k, int max_repeat, uint32_t* seq_cnt)
@@ -707,13 +686,7 @@ __global__ void __launch_bounds__(FIND_WAVES * 64) k_het_judge(Index ix, const u
         left = (uint32_t)__shfl((int)(uint32_t)hq, (int)i, 64);
         const uint32_t L = len[s], right = p + i;
         bool right_ok = (uint64_t)right + (uint32_t)k <= L;
-        if (right_ok && bad) { /* as k_profile: the k bits of the characters right .. right + k - 1 */
-            const uint64_t* bw = bad + o;
-            const uint32_t sh = right & 63u;
-            uint64_t m = bw[right >> 6] >> sh;
-            if (sh + (uint32_t)k > 64u) m |= bw[(right >> 6) + 1] << (64u - sh);
-            right_ok = (m & ((1ull << k) - 1ull)) == 0;
-        }
+        if (right_ok && bad) right_ok = !covers_bad(bad + o, right, k);
         if (right_ok) {
             uint32_t lines = 0;
             found = find_micro_assembly(ix, le_kmer(w, left, mk), le_kmer(w, right, mk), lane, lines);
@@ -735,8 +708,8 @@ __global__ void __launch_bounds__(FIND_WAVES * 64) k_het_judge(Index ix, const u
     }
     if (lane == 0) {
         e[c].out = out; e[c].rep = i; e[c].left = left; e[c].ins = found >= 0 ? (uint32_t)found : 0u;
-        if (bal) atomicAdd(&counters[0], 1ull);
-        if (out == HET_SITE) atomicAdd(&counters[1], 1ull);
+        if (bal) atomicAdd(&counters[CNT_HET_CANDIDATES], 1ull);
+        if (out == HET_SITE) atomicAdd(&counters[CNT_HET_RAW_SITES], 1ull);
     }
 }
 __global__ void __launch_bounds__(RUNS_BLOCK) k_het_chain(HetEntry* e, uint64_t n, const uint64_t* __restrict__ vbits, const uint64_t* __restrict__ word_off, int max_repeat)
@@ -754,12 +727,12 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_het_final(const HetEntry* __rest
     uint32_t keep = 0;
     if (out == HET_SITE) {
         keep = e[c].state == HET_ACCEPTED;
-        atomicAdd(&counters[keep ? (e[c].rep ? 5 : 4) : 3], 1ull);
+        atomicAdd(&counters[keep ? (e[c].rep ? CNT_HET_FUZZY : CNT_HET_CLEAN) : CNT_HET_SUPPRESSED], 1ull);
     } else if (out != HET_NONE) {
         const bool quiet = het_suppressed(e, vbits, word_off, c, (uint32_t)max_repeat);
         keep = out == HET_INS && !quiet;
-        if (out == HET_INS) atomicAdd(&counters[quiet ? 3 : 6], 1ull);
-        else if (!quiet) atomicAdd(&counters[2], 1ull);
+        if (out == HET_INS) atomicAdd(&counters[quiet ? CNT_HET_SUPPRESSED : CNT_HET_SMALL], 1ull);
+        else if (!quiet) atomicAdd(&counters[CNT_HET_FILTERED], 1ull);
     }
     mark[c] = keep;
 }
@@ -993,42 +966,92 @@ int nw_run(const mtg_index* idx, const std::vector<NwPair>& pairs, std::vector<u
     return MTG_OK;
 }
 
+namespace {
+/* The packed sequences of scan_run / profile_run / find_homo_run / find_het_run as their kernels read them: words, word_off and len, and where
+ * the run has them the bad plane, the rep plane (both of nwords words) and pos_off (one per sequence).  upload: the caller's arrays are host
+ * memory and go to buffers of our own; take: they are device memory and are used as they are */
+struct SeqInput {
+    const uint64_t *words = nullptr, *word_off = nullptr, *bad = nullptr, *rep = nullptr, *pos_off = nullptr;
+    const uint32_t* len = nullptr;
+    size_t nwords = 0, nseq = 0;
+    bool on_device = false;
+    DevBuf d_words, d_word_off, d_len, d_bad, d_rep, d_pos_off;
+
+    void take(const uint64_t* w, const uint64_t* off, const uint32_t* l, size_t n, const uint64_t* b = nullptr, const uint64_t* r = nullptr, const uint64_t* po = nullptr)
+    {
+        words = w; word_off = off; len = l; nseq = n; bad = b; rep = r; pos_off = po;
+        on_device = true;
+    }
+    int upload(const uint64_t* w, size_t nw, const uint64_t* off, const uint32_t* l, size_t n, const uint64_t* b = nullptr, const uint64_t* r = nullptr, const uint64_t* po = nullptr)
+    {
+        nwords = nw; nseq = n;
+        if (int rc = up(d_words, w, nw, words)) return rc;
+        if (int rc = up(d_word_off, off, n, word_off)) return rc;
+        if (int rc = up(d_len, l, n, len)) return rc;
+        if (b) { if (int rc = up(d_bad, b, nw, bad)) return rc; }
+        if (r) { if (int rc = up(d_rep, r, nw, rep)) return rc; }
+        if (po) { if (int rc = up(d_pos_off, po, n, pos_off)) return rc; }
+        return MTG_OK;
+    }
+    /* the planes take a word per 64 positions at the sequence's word offset: how many words they span.  Of device arrays the offsets and
+     * lengths come to the host for that (two copies that wait for the device) */
+    int plane_words(size_t* n) const
+    {
+        *n = nwords;
+        if (!on_device) return MTG_OK;
+        std::vector<uint64_t> ho(nseq);
+        std::vector<uint32_t> hl(nseq);
+        HIP_TRY(hipMemcpy(ho.data(), word_off, nseq * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hl.data(), len, nseq * 4, hipMemcpyDeviceToHost));
+        size_t reach = 0;
+        for (size_t s = 0; s < nseq; s++) reach = std::max<size_t>(reach, (size_t)ho[s] + hl[s] / 64 + 1);
+        *n = reach;
+        return MTG_OK;
+    }
+
+private:
+    template <typename T> static int up(DevBuf& d, const T* src, size_t count, const T*& dev)
+    {
+        HIP_TRY(d.alloc(count * sizeof(T)));
+        HIP_TRY(hipMemcpy(d.p, src, count * sizeof(T), hipMemcpyHostToDevice));
+        dev = d.as<T>();
+        return MTG_OK;
+    }
+};
+} // namespace
+
 int scan_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, int mode, uint64_t* out_bits,
              int device_ptrs, mtg_scan_stats* st)
 {
     if (int rc = use_device_of(idx)) return rc;
     if (!idx || !idx->dev.bloom.bits) { set_error("the index has no Bloom filter (MTG_BLOOM_BITS=0)"); return MTG_ERR_ARG; }
     if (nseq == 0) return MTG_OK;
-    DevBuf d_w, d_o, d_l, d_b, d_c;
-    const uint64_t *pw = words, *po = word_off;
-    const uint32_t* pl = len;
+    SeqInput in;
+    DevBuf d_b, d_c;
     uint64_t* pb = out_bits;
-    if (!device_ptrs) {
-        HIP_TRY(d_w.alloc(nwords * 8)); HIP_TRY(d_o.alloc(nseq * 8)); HIP_TRY(d_l.alloc(nseq * 4)); HIP_TRY(d_b.alloc(nwords * 8));
-        HIP_TRY(hipMemcpy(d_w.p, words, nwords * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_o.p, word_off, nseq * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_l.p, len, nseq * 4, hipMemcpyHostToDevice));
+    if (device_ptrs) in.take(words, word_off, len, nseq); /* (no plane_words here: the device entry makes no copy and does not wait) */
+    else {
+        if (int rc = in.upload(words, nwords, word_off, len, nseq)) return rc;
+        HIP_TRY(d_b.alloc(nwords * 8));
         HIP_TRY(hipMemset(d_b.p, 0, nwords * 8));
-        pw = d_w.as<uint64_t>(); po = d_o.as<uint64_t>(); pl = d_l.as<uint32_t>(); pb = d_b.as<uint64_t>();
+        pb = d_b.as<uint64_t>();
     }
-    HIP_TRY(d_c.alloc(32));
-    HIP_TRY(hipMemset(d_c.p, 0, 32));
+    HIP_TRY(d_c.alloc(SCAN_COUNTERS * 8));
+    HIP_TRY(hipMemset(d_c.p, 0, SCAN_COUNTERS * 8));
+    EventSet events;
     hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(events.make(e0)); HIP_TRY(events.make(e1));
     HIP_TRY(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(k_scan, dim3((unsigned)std::min<size_t>(nseq, 256 * 16)), dim3(SCAN_TILE), 0, 0, idx->dev, pw, po, pl, nseq, mode, pb, d_c.as<unsigned long long>());
+    hipLaunchKernelGGL(k_scan, dim3((unsigned)std::min<size_t>(nseq, 256 * 16)), dim3(SCAN_TILE), 0, 0, idx->dev, in.words, in.word_off, in.len, nseq, mode, pb, d_c.as<unsigned long long>());
     HIP_TRY(hipEventRecord(e1, 0));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventSynchronize(e1));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    unsigned long long c[4];
-    HIP_TRY(hipMemcpy(c, d_c.p, 32, hipMemcpyDeviceToHost));
+    unsigned long long c[SCAN_COUNTERS];
+    HIP_TRY(hipMemcpy(c, d_c.p, SCAN_COUNTERS * 8, hipMemcpyDeviceToHost));
     if (!device_ptrs) HIP_TRY(hipMemcpy(out_bits, pb, nwords * 8, hipMemcpyDeviceToHost));
-    if (st) { st->n_kmers = c[0]; st->bloom_positive = c[1]; st->confirmed = c[2]; st->blocks_staged = c[3]; st->kernel_ms = ms; }
+    if (st) { st->n_kmers = c[SCAN_KMERS]; st->bloom_positive = c[SCAN_BLOOM_POSITIVE]; st->confirmed = c[SCAN_CONFIRMED]; st->blocks_staged = c[SCAN_BLOCKS_STAGED]; st->kernel_ms = ms; }
     return MTG_OK;
 }
 
@@ -1043,48 +1066,33 @@ int profile_run(const mtg_index* idx, const uint64_t* words, size_t nwords, cons
     if (st) *st = mtg_profile_stats{};
     if (nseq == 0) return MTG_OK;
     const int k = idx->dev.k;
-    DevBuf d_w, d_o, d_l, d_bad, d_po, d_out, d_v, d_p, d_cnt, d_before, d_c, d_runs;
-    const uint64_t *pw = words, *po = word_off, *pbad = bad, *ppo = pos_off;
-    const uint32_t* pl = len;
+    SeqInput in;
+    DevBuf d_out, d_v, d_p, d_cnt, d_before, d_c, d_runs;
     uint32_t* pout = out;
-    if (!device_ptrs) {
-        HIP_TRY(d_w.alloc(nwords * 8)); HIP_TRY(d_o.alloc(nseq * 8)); HIP_TRY(d_l.alloc(nseq * 4));
-        HIP_TRY(hipMemcpy(d_w.p, words, nwords * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_o.p, word_off, nseq * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_l.p, len, nseq * 4, hipMemcpyHostToDevice));
-        pw = d_w.as<uint64_t>(); po = d_o.as<uint64_t>(); pl = d_l.as<uint32_t>();
-        if (bad) { HIP_TRY(d_bad.alloc(nwords * 8)); HIP_TRY(hipMemcpy(d_bad.p, bad, nwords * 8, hipMemcpyHostToDevice)); pbad = d_bad.as<uint64_t>(); }
-        if (out) {
-            HIP_TRY(d_po.alloc(nseq * 8)); HIP_TRY(hipMemcpy(d_po.p, pos_off, nseq * 8, hipMemcpyHostToDevice));
-            HIP_TRY(d_out.alloc(npos_total * 4));
-            ppo = d_po.as<uint64_t>(); pout = d_out.as<uint32_t>();
-        }
-    } else { /* the planes take a word per 64 positions at the sequence's word offset: how far they reach */
-        std::vector<uint64_t> ho(nseq);
-        std::vector<uint32_t> hl(nseq);
-        HIP_TRY(hipMemcpy(ho.data(), word_off, nseq * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(hl.data(), len, nseq * 4, hipMemcpyDeviceToHost));
-        nwords = 0;
-        for (size_t s = 0; s < nseq; s++) nwords = std::max<size_t>(nwords, (size_t)ho[s] + hl[s] / 64 + 1);
+    if (device_ptrs) in.take(words, word_off, len, nseq, bad, nullptr, pos_off);
+    else {
+        if (int rc = in.upload(words, nwords, word_off, len, nseq, bad, nullptr, out ? pos_off : nullptr)) return rc;
+        if (out) { HIP_TRY(d_out.alloc(npos_total * 4)); pout = d_out.as<uint32_t>(); }
     }
+    if (int rc = in.plane_words(&nwords)) return rc;
     HIP_TRY(d_v.alloc(nwords * 8)); HIP_TRY(d_p.alloc(nwords * 8));
     HIP_TRY(d_cnt.alloc(nseq * 4)); HIP_TRY(d_before.alloc(nseq * 8));
-    HIP_TRY(d_c.alloc(64));
-    HIP_TRY(hipMemset(d_c.p, 0, 64));
-    unsigned long long* cnt = d_c.as<unsigned long long>(); /* [0..2] k_profile's counters, [4] runs, [5] longest */
+    HIP_TRY(d_c.alloc(CNT_PROFILE_SLOTS * 8));
+    HIP_TRY(hipMemset(d_c.p, 0, CNT_PROFILE_SLOTS * 8));
+    unsigned long long* cnt = d_c.as<unsigned long long>();
     EventSet events;
     hipEvent_t e0, e1, e2, e3;
     HIP_TRY(events.make(e0)); HIP_TRY(events.make(e1)); HIP_TRY(events.make(e2)); HIP_TRY(events.make(e3));
     const dim3 grid((unsigned)std::min<size_t>(nseq, 256 * 16));
     HIP_TRY(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(k_profile<false>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, pw, po, pl, nseq, pbad, ppo, pout, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
-    hipLaunchKernelGGL(k_profile_count<false>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_cnt.as<uint32_t>());
-    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + 4);
+    hipLaunchKernelGGL(k_profile<false>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, in.words, in.word_off, in.len, nseq, in.bad, in.pos_off, pout, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
+    hipLaunchKernelGGL(k_profile_count<false>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, d_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + CNT_RUNS);
     HIP_TRY(hipEventRecord(e1, 0));
     HIP_TRY(hipGetLastError());
-    unsigned long long c[8];
-    HIP_TRY(hipMemcpy(c, d_c.p, 64, hipMemcpyDeviceToHost));
-    const uint64_t total = c[4];
+    unsigned long long c[CNT_PROFILE_SLOTS];
+    HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
+    const uint64_t total = c[CNT_RUNS];
     /* every run is written (the longest one may lie past runs_cap): into the caller's device array when it holds them all, else into one of our own */
     mtg_run* pr = runs;
     if (!device_ptrs || total > runs_cap) { HIP_TRY(d_runs.alloc((size_t)total * sizeof(mtg_run))); pr = d_runs.as<mtg_run>(); }
@@ -1092,20 +1100,20 @@ int profile_run(const mtg_index* idx, const uint64_t* words, size_t nwords, cons
     if (total) {
         HIP_TRY(hipMemset(pr, 0, (size_t)total * sizeof(mtg_run)));
         HIP_TRY(hipEventRecord(e2, 0));
-        hipLaunchKernelGGL(k_profile_write<false>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_before.as<uint64_t>(), pr, total);
-        hipLaunchKernelGGL(k_profile_finish, dim3((unsigned)std::min<uint64_t>((total + RUNS_BLOCK - 1) / RUNS_BLOCK, 256 * 16)), dim3(RUNS_BLOCK), 0, 0, pr, total, cnt + 4);
+        hipLaunchKernelGGL(k_profile_write<false>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, d_before.as<uint64_t>(), pr, total);
+        hipLaunchKernelGGL(k_profile_finish, dim3((unsigned)std::min<uint64_t>((total + RUNS_BLOCK - 1) / RUNS_BLOCK, 256 * 16)), dim3(RUNS_BLOCK), 0, 0, pr, total, cnt + CNT_RUNS);
         HIP_TRY(hipEventRecord(e3, 0));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventSynchronize(e3));
         HIP_TRY(hipEventElapsedTime(&ms1, e2, e3));
-        HIP_TRY(hipMemcpy(c, d_c.p, 64, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
         const size_t ncopy = (size_t)std::min<uint64_t>(total, runs_cap);
         if (ncopy && pr != runs) HIP_TRY(hipMemcpy(runs, pr, ncopy * sizeof(mtg_run), device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     }
     HIP_TRY(hipEventElapsedTime(&ms0, e0, e1));
     if (!device_ptrs && out) HIP_TRY(hipMemcpy(out, pout, npos_total * 4, hipMemcpyDeviceToHost));
     *n_runs = (size_t)total;
-    if (st) { st->n_positions = c[0]; st->n_valid = c[1]; st->n_present = c[2]; st->n_runs = total; st->longest_run = total ? c[5] : 0; st->kernel_ms = (double)ms0 + (double)ms1; }
+    if (st) { st->n_positions = c[CNT_POSITIONS]; st->n_valid = c[CNT_VALID]; st->n_present = c[CNT_PRESENT]; st->n_runs = total; st->longest_run = total ? c[CNT_RUNS_LONGEST] : 0; st->kernel_ms = (double)ms0 + (double)ms1; }
     return MTG_OK;
 }
 
@@ -1140,45 +1148,32 @@ int find_homo_run(const mtg_index* idx, const uint64_t* words, size_t nwords, co
     if (nseq == 0) return MTG_OK;
     const int k = idx->dev.k;
     if (max_repeat > k - 2) max_repeat = k - 2;
-    DevBuf d_w, d_o, d_l, d_bad, d_v, d_p, d_cnt, d_before, d_c, d_gaps, d_mark, d_blk_cnt, d_blk_before, d_cand, d_res, d_sel, d_calls;
-    const uint64_t *pw = words, *po = word_off, *pbad = bad;
-    const uint32_t* pl = len;
-    if (!device_ptrs) {
-        HIP_TRY(d_w.alloc(nwords * 8)); HIP_TRY(d_o.alloc(nseq * 8)); HIP_TRY(d_l.alloc(nseq * 4));
-        HIP_TRY(hipMemcpy(d_w.p, words, nwords * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_o.p, word_off, nseq * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_l.p, len, nseq * 4, hipMemcpyHostToDevice));
-        pw = d_w.as<uint64_t>(); po = d_o.as<uint64_t>(); pl = d_l.as<uint32_t>();
-        if (bad) { HIP_TRY(d_bad.alloc(nwords * 8)); HIP_TRY(hipMemcpy(d_bad.p, bad, nwords * 8, hipMemcpyHostToDevice)); pbad = d_bad.as<uint64_t>(); }
-    } else { /* as profile_run: how far the planes reach */
-        std::vector<uint64_t> ho(nseq);
-        std::vector<uint32_t> hl(nseq);
-        HIP_TRY(hipMemcpy(ho.data(), word_off, nseq * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(hl.data(), len, nseq * 4, hipMemcpyDeviceToHost));
-        nwords = 0;
-        for (size_t s = 0; s < nseq; s++) nwords = std::max<size_t>(nwords, (size_t)ho[s] + hl[s] / 64 + 1);
-    }
+    SeqInput in;
+    DevBuf d_v, d_p, d_cnt, d_before, d_c, d_gaps, d_mark, d_blk_cnt, d_blk_before, d_cand, d_res, d_sel, d_calls;
+    if (device_ptrs) in.take(words, word_off, len, nseq, bad);
+    else if (int rc = in.upload(words, nwords, word_off, len, nseq, bad)) return rc;
+    if (int rc = in.plane_words(&nwords)) return rc;
     HIP_TRY(d_v.alloc(nwords * 8)); HIP_TRY(d_p.alloc(nwords * 8));
     HIP_TRY(d_cnt.alloc(nseq * 4)); HIP_TRY(d_before.alloc(nseq * 8));
-    HIP_TRY(d_c.alloc(128));
-    HIP_TRY(hipMemset(d_c.p, 0, 128));
-    unsigned long long* cnt = d_c.as<unsigned long long>(); /* [0..2] k_profile's counters, [4] gaps of any kind, [5] the longest, [6] candidates, [7] calls, [8] gaps seen, [10..13] the four kinds */
+    HIP_TRY(d_c.alloc(CNT_HOMO_SLOTS * 8));
+    HIP_TRY(hipMemset(d_c.p, 0, CNT_HOMO_SLOTS * 8));
+    unsigned long long* cnt = d_c.as<unsigned long long>(); /* (CNT_GAPS: gaps of any kind) */
     EventSet events;
     hipEvent_t ev[8];
     for (hipEvent_t& e : ev) HIP_TRY(events.make(e));
     const dim3 grid((unsigned)std::min<size_t>(nseq, 256 * 16));
-    unsigned long long c[16];
+    unsigned long long c[CNT_HOMO_SLOTS];
     float ms = 0, part = 0;
     /* 1. the planes, the gaps counted */
     HIP_TRY(hipEventRecord(ev[0], 0));
-    hipLaunchKernelGGL(k_profile<false>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, pw, po, pl, nseq, pbad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
-    hipLaunchKernelGGL(k_profile_count<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_cnt.as<uint32_t>());
-    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + 4);
+    hipLaunchKernelGGL(k_profile<false>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, in.words, in.word_off, in.len, nseq, in.bad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
+    hipLaunchKernelGGL(k_profile_count<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, d_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + CNT_GAPS);
     HIP_TRY(hipEventRecord(ev[1], 0));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(c, d_c.p, 128, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
     HIP_TRY(hipEventElapsedTime(&part, ev[0], ev[1])); ms += part;
-    const uint64_t n_gaps_all = c[4];
+    const uint64_t n_gaps_all = c[CNT_GAPS];
     if (n_gaps_all > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 gaps"); return MTG_ERR_ARG; }
     uint64_t n_cand = 0, total = 0;
     if (n_gaps_all) {
@@ -1188,19 +1183,19 @@ int find_homo_run(const mtg_index* idx, const uint64_t* words, size_t nwords, co
         HIP_TRY(d_mark.alloc((size_t)n_gaps_all * 4));
         const unsigned gb = (unsigned)((n_gaps_all + RUNS_BLOCK - 1) / RUNS_BLOCK);
         HIP_TRY(hipEventRecord(ev[2], 0));
-        hipLaunchKernelGGL(k_profile_write<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), po, pl, nseq, k, d_before.as<uint64_t>(), d_gaps.as<mtg_run>(), n_gaps_all);
-        hipLaunchKernelGGL(k_profile_finish, dim3(std::min(gb, 256u * 16u)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, cnt + 4);
-        hipLaunchKernelGGL(k_find_mark, dim3(gb), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, k, max_repeat, d_mark.as<uint32_t>(), cnt + 8);
-        if (int rc = mark_compact(d_mark.as<uint32_t>(), n_gaps_all, d_blk_cnt, d_blk_before, cnt + 6, d_cand, ~0ull, &n_cand)) return rc;
+        hipLaunchKernelGGL(k_profile_write<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, d_before.as<uint64_t>(), d_gaps.as<mtg_run>(), n_gaps_all);
+        hipLaunchKernelGGL(k_profile_finish, dim3(std::min(gb, 256u * 16u)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, cnt + CNT_GAPS);
+        hipLaunchKernelGGL(k_find_mark, dim3(gb), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, k, max_repeat, d_mark.as<uint32_t>(), cnt);
+        if (int rc = mark_compact(d_mark.as<uint32_t>(), n_gaps_all, d_blk_cnt, d_blk_before, cnt + CNT_HOMO_CANDIDATES, d_cand, ~0ull, &n_cand)) return rc;
         HIP_TRY(hipEventRecord(ev[3], 0));
     }
     if (n_cand) {
         /* 3. the observers, one wave per candidate; the calls listed in order and written */
         HIP_TRY(d_res.alloc((size_t)n_cand * 4));
         HIP_TRY(hipEventRecord(ev[4], 0));
-        hipLaunchKernelGGL(k_find_assemble, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, pw, po, pl, pbad, d_gaps.as<mtg_run>(),
-                           d_cand.as<uint32_t>(), n_cand, d_res.as<uint32_t>(), cnt + 8);
-        if (int rc = mark_compact(d_res.as<uint32_t>(), n_cand, d_blk_cnt, d_blk_before, cnt + 7, d_sel, cap, &total)) return rc;
+        hipLaunchKernelGGL(k_find_assemble, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, in.words, in.word_off, in.len, in.bad, d_gaps.as<mtg_run>(),
+                           d_cand.as<uint32_t>(), n_cand, d_res.as<uint32_t>(), cnt);
+        if (int rc = mark_compact(d_res.as<uint32_t>(), n_cand, d_blk_cnt, d_blk_before, cnt + CNT_HOMO_CALLS, d_sel, cap, &total)) return rc;
         const uint64_t keep = std::min<uint64_t>(total, cap);
         mtg_find_call* pc = calls;
         if (keep) {
@@ -1218,11 +1213,11 @@ int find_homo_run(const mtg_index* idx, const uint64_t* words, size_t nwords, co
         HIP_TRY(hipEventSynchronize(ev[3]));
         HIP_TRY(hipEventElapsedTime(&part, ev[2], ev[3])); ms += part;
     }
-    HIP_TRY(hipMemcpy(c, d_c.p, 128, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
     *n_calls = (size_t)total;
     if (st) {
-        st->n_positions = c[0]; st->n_gaps = c[8]; st->n_candidates = n_cand;
-        st->n_homo_clean = c[10]; st->n_homo_fuzzy = c[11]; st->n_small_clean = c[12]; st->n_small_fuzzy = c[13];
+        st->n_positions = c[CNT_POSITIONS]; st->n_gaps = c[CNT_GAPS_SEEN]; st->n_candidates = n_cand;
+        st->n_homo_clean = c[CNT_HOMO_CLEAN]; st->n_homo_fuzzy = c[CNT_HOMO_FUZZY]; st->n_small_clean = c[CNT_SMALL_CLEAN]; st->n_small_fuzzy = c[CNT_SMALL_FUZZY];
         st->kernel_ms = (double)ms;
     }
     return MTG_OK;
@@ -1241,47 +1236,33 @@ int find_het_run(const mtg_index* idx, const uint64_t* words, size_t nwords, con
     if (nseq == 0) return MTG_OK;
     const int k = idx->dev.k;
     if (max_repeat > k - 2) max_repeat = k - 2;
-    DevBuf d_w, d_o, d_l, d_bad, d_rep, d_v, d_p, d_in2, d_out2, d_br, d_cnt, d_before, d_c, d_e, d_mark, d_blk_cnt, d_blk_before, d_sel, d_calls;
-    const uint64_t *pw = words, *po = word_off, *pbad = bad, *prep = rep;
-    const uint32_t* pl = len;
-    if (!device_ptrs) {
-        HIP_TRY(d_w.alloc(nwords * 8)); HIP_TRY(d_o.alloc(nseq * 8)); HIP_TRY(d_l.alloc(nseq * 4));
-        HIP_TRY(hipMemcpy(d_w.p, words, nwords * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_o.p, word_off, nseq * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_l.p, len, nseq * 4, hipMemcpyHostToDevice));
-        pw = d_w.as<uint64_t>(); po = d_o.as<uint64_t>(); pl = d_l.as<uint32_t>();
-        if (bad) { HIP_TRY(d_bad.alloc(nwords * 8)); HIP_TRY(hipMemcpy(d_bad.p, bad, nwords * 8, hipMemcpyHostToDevice)); pbad = d_bad.as<uint64_t>(); }
-        if (rep) { HIP_TRY(d_rep.alloc(nwords * 8)); HIP_TRY(hipMemcpy(d_rep.p, rep, nwords * 8, hipMemcpyHostToDevice)); prep = d_rep.as<uint64_t>(); }
-    } else { /* as profile_run: how far the planes reach */
-        std::vector<uint64_t> ho(nseq);
-        std::vector<uint32_t> hl(nseq);
-        HIP_TRY(hipMemcpy(ho.data(), word_off, nseq * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(hl.data(), len, nseq * 4, hipMemcpyDeviceToHost));
-        nwords = 0;
-        for (size_t s = 0; s < nseq; s++) nwords = std::max<size_t>(nwords, (size_t)ho[s] + hl[s] / 64 + 1);
-    }
+    SeqInput in;
+    DevBuf d_v, d_p, d_in2, d_out2, d_br, d_cnt, d_before, d_c, d_e, d_mark, d_blk_cnt, d_blk_before, d_sel, d_calls;
+    if (device_ptrs) in.take(words, word_off, len, nseq, bad, rep);
+    else if (int rc = in.upload(words, nwords, word_off, len, nseq, bad, rep)) return rc;
+    if (int rc = in.plane_words(&nwords)) return rc;
     HIP_TRY(d_v.alloc(nwords * 8)); HIP_TRY(d_p.alloc(nwords * 8)); HIP_TRY(d_in2.alloc(nwords * 8)); HIP_TRY(d_out2.alloc(nwords * 8)); HIP_TRY(d_br.alloc(nwords * 8));
     HIP_TRY(d_cnt.alloc(nseq * 4)); HIP_TRY(d_before.alloc(nseq * 8));
-    HIP_TRY(d_c.alloc(128));
-    HIP_TRY(hipMemset(d_c.p, 0, 128));
-    unsigned long long* cnt = d_c.as<unsigned long long>(); /* [0..2] k_profile's counters, [4] candidates listed, [6] calls, [8..14] the counters of k_het_judge / k_het_final */
+    HIP_TRY(d_c.alloc(CNT_HET_SLOTS * 8));
+    HIP_TRY(hipMemset(d_c.p, 0, CNT_HET_SLOTS * 8));
+    unsigned long long* cnt = d_c.as<unsigned long long>();
     EventSet events;
     hipEvent_t ev[4];
     for (hipEvent_t& e : ev) HIP_TRY(events.make(e));
     const dim3 grid((unsigned)std::min<size_t>(nseq, 256 * 16));
-    unsigned long long c[16];
+    unsigned long long c[CNT_HET_SLOTS];
     float ms = 0, part = 0;
     /* 1. the planes, the candidates counted */
     HIP_TRY(hipEventRecord(ev[0], 0));
-    hipLaunchKernelGGL(k_profile<true>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, pw, po, pl, nseq, pbad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt,
+    hipLaunchKernelGGL(k_profile<true>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, in.words, in.word_off, in.len, nseq, in.bad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt,
                        d_in2.as<uint64_t>(), d_out2.as<uint64_t>(), d_br.as<uint64_t>());
-    hipLaunchKernelGGL(k_het_count, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_in2.as<uint64_t>(), d_out2.as<uint64_t>(), prep, po, pl, nseq, k, max_repeat, d_cnt.as<uint32_t>());
-    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + 4);
+    hipLaunchKernelGGL(k_het_count, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_in2.as<uint64_t>(), d_out2.as<uint64_t>(), in.rep, in.word_off, in.len, nseq, k, max_repeat, d_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + CNT_HET_LISTED);
     HIP_TRY(hipEventRecord(ev[1], 0));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(c, d_c.p, 128, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
     HIP_TRY(hipEventElapsedTime(&part, ev[0], ev[1])); ms += part;
-    const uint64_t n_cand = c[4];
+    const uint64_t n_cand = c[CNT_HET_LISTED];
     if (n_cand > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 candidates"); return MTG_ERR_ARG; }
     uint64_t total = 0;
     if (n_cand) {
@@ -1291,13 +1272,13 @@ int find_het_run(const mtg_index* idx, const uint64_t* words, size_t nwords, con
         HIP_TRY(d_mark.alloc((size_t)n_cand * 4));
         const unsigned cb = (unsigned)((n_cand + RUNS_BLOCK - 1) / RUNS_BLOCK);
         HIP_TRY(hipEventRecord(ev[2], 0));
-        hipLaunchKernelGGL(k_het_list, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_in2.as<uint64_t>(), d_out2.as<uint64_t>(), prep, po, pl, nseq, k, max_repeat, d_before.as<uint64_t>(),
+        hipLaunchKernelGGL(k_het_list, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_in2.as<uint64_t>(), d_out2.as<uint64_t>(), in.rep, in.word_off, in.len, nseq, k, max_repeat, d_before.as<uint64_t>(),
                            d_e.as<HetEntry>(), n_cand);
-        hipLaunchKernelGGL(k_het_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, pw, po, pl, pbad, d_v.as<uint64_t>(), d_out2.as<uint64_t>(),
-                           d_br.as<uint64_t>(), prep, d_e.as<HetEntry>(), n_cand, max_repeat, branching_filter, cnt + 8);
-        hipLaunchKernelGGL(k_het_chain, dim3(cb), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), n_cand, d_v.as<uint64_t>(), po, max_repeat);
-        hipLaunchKernelGGL(k_het_final, dim3(cb), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), n_cand, d_v.as<uint64_t>(), po, max_repeat, d_mark.as<uint32_t>(), cnt + 8);
-        if (int rc = mark_compact(d_mark.as<uint32_t>(), n_cand, d_blk_cnt, d_blk_before, cnt + 6, d_sel, cap, &total)) return rc;
+        hipLaunchKernelGGL(k_het_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, in.words, in.word_off, in.len, in.bad, d_v.as<uint64_t>(), d_out2.as<uint64_t>(),
+                           d_br.as<uint64_t>(), in.rep, d_e.as<HetEntry>(), n_cand, max_repeat, branching_filter, cnt);
+        hipLaunchKernelGGL(k_het_chain, dim3(cb), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), n_cand, d_v.as<uint64_t>(), in.word_off, max_repeat);
+        hipLaunchKernelGGL(k_het_final, dim3(cb), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), n_cand, d_v.as<uint64_t>(), in.word_off, max_repeat, d_mark.as<uint32_t>(), cnt);
+        if (int rc = mark_compact(d_mark.as<uint32_t>(), n_cand, d_blk_cnt, d_blk_before, cnt + CNT_HET_CALLS, d_sel, cap, &total)) return rc;
         const uint64_t keep = std::min<uint64_t>(total, cap);
         mtg_find_call* pc = calls;
         if (keep) {
@@ -1309,12 +1290,12 @@ int find_het_run(const mtg_index* idx, const uint64_t* words, size_t nwords, con
         HIP_TRY(hipEventSynchronize(ev[3]));
         if (keep && !device_ptrs) HIP_TRY(hipMemcpy(calls, pc, (size_t)keep * sizeof(mtg_find_call), hipMemcpyDeviceToHost));
         HIP_TRY(hipEventElapsedTime(&part, ev[2], ev[3])); ms += part;
-        HIP_TRY(hipMemcpy(c, d_c.p, 128, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
     }
     *n_calls = (size_t)total;
     if (st) {
-        st->n_positions = c[0]; st->n_candidates = c[8]; st->n_raw_sites = c[9]; st->n_filtered = c[10]; st->n_suppressed = c[11];
-        st->n_het_clean = c[12]; st->n_het_fuzzy = c[13]; st->n_het_small = c[14];
+        st->n_positions = c[CNT_POSITIONS]; st->n_candidates = c[CNT_HET_CANDIDATES]; st->n_raw_sites = c[CNT_HET_RAW_SITES]; st->n_filtered = c[CNT_HET_FILTERED]; st->n_suppressed = c[CNT_HET_SUPPRESSED];
+        st->n_het_clean = c[CNT_HET_CLEAN]; st->n_het_fuzzy = c[CNT_HET_FUZZY]; st->n_het_small = c[CNT_HET_SMALL];
         st->kernel_ms = (double)ms;
     }
     return MTG_OK;

@@ -9,6 +9,9 @@
  * holds a word numbers its firsts from the firsts before the word, its lasts from the same count less one when a run is open across the
  * word's lower seam, and writes its half of each record -- no thread ever looks further than the two neighbouring words, whatever the length
  * of the run.
+ *
+ * Also here, as word logic on a plane of the same layout: covers_bad, the test of k_profile, k_find_assemble and k_het_judge for a k-mer that
+ * covers a character that is no nucleotide.
  */
 #ifndef MTG_PROFILE_RUNS_H
 #define MTG_PROFILE_RUNS_H
@@ -33,6 +36,16 @@ MTG_DEV uint64_t run_plane_word(const uint64_t* plane, uint32_t w, uint32_t nw, 
     if (w >= nw) return 0ull;
     const uint64_t x = plane[w];
     return (w + 1u == nw && (npos & 63u)) ? (x & ((1ull << (npos & 63u)) - 1ull)) : x;
+}
+
+/* do the k characters from position p (k <= 32) hold one that is no nucleotide: any of the k bits from p of the bad plane (one bit per
+ * CHARACTER, same layout).  At most two words; the second is read only when the bits reach into it */
+MTG_DEV bool covers_bad(const uint64_t* bw, uint32_t p, int k)
+{
+    const uint32_t sh = p & 63u;
+    uint64_t m = bw[p >> 6] >> sh;
+    if (sh + (uint32_t)k > 64u) m |= bw[(p >> 6) + 1] << (64u - sh);
+    return (m & ((1ull << k) - 1ull)) != 0;
 }
 
 MTG_DEV RunWord run_word(const uint64_t* vplane, const uint64_t* pplane, uint32_t w, uint32_t npos)

@@ -10,6 +10,8 @@
 #include "emu_us.h"
 #include "emu_walk.h"
 #include <atomic>
+#include <chrono>
+#include <condition_variable>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -399,8 +401,23 @@ int device_run(const mtg_index* idx, const mtg_params* p, const FillInput& in, R
 {
     if (while_busy) (*while_busy)();
     /* TEST-ONLY fault injection: every batch on the named pretended device fails (the tool's multi-device driver must stop and report) */
-    if (const char* e = getenv("MTG_EMU_FAIL_DEVICE"))
-        if (atoi(e) == idx->device) { set_error("injected failure on device %d", idx->device); return MTG_ERR_NOMEM; }
+    {
+        /* Which device's threads win the tool's next batch is a matter of scheduling, and the named device may win none before the input is
+         * used up (then nothing fails).  So the batches of the other devices wait here until the named one has had its first: their threads
+         * hold a batch each, the next one goes to a thread of the named device.  The wait is bounded for a device the run does not have. */
+        static std::mutex fm;
+        static std::condition_variable fcv;
+        static bool failed_once = false;
+        std::unique_lock<std::mutex> lk(fm);
+        const char* e = getenv("MTG_EMU_FAIL_DEVICE");
+        if (!e) failed_once = false; /* a run without the injection comes before every run with it */
+        else if (atoi(e) == idx->device) {
+            failed_once = true;
+            fcv.notify_all();
+            set_error("injected failure on device %d", idx->device);
+            return MTG_ERR_NOMEM;
+        } else fcv.wait_for(lk, std::chrono::seconds(5), [&] { return failed_once; });
+    }
     const int k = idx->dev.k;
     const size_t n = in.src.size();
     /* stand-in for k_encode_targets, or (mtg_fill_text) for k_marshal_text and k_marshal_targets: the same per-gap functions, from the text block */

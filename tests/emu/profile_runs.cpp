@@ -9,7 +9,10 @@
  *      against the seams of the 64-bit words and of the 256-position tiles -- with a present, an invalid or no position on either side;
  *   2. random planes of 0 .. 1100 positions, several sequences per case at arbitrary word offsets, densities from "almost all present" to
  *      "almost all absent", invalid positions sprinkled in, junk in the bits past the last position, capacities below the number of runs.
- * Prints "OK <cases> cases <runs> runs".
+ *   3. covers_bad (the bad-bit test of k_profile, k_find_assemble and k_het_judge) against a loop over the k bits: every k in 11 .. 32 from
+ *      every p in 0 .. 130, on planes that are random, all zero, and zero but for one bit at p - 1, p, p + k - 1 or p + k, in an array that
+ *      ends with the last word the function may read (under AddressSanitizer a read behind it is an error).
+ * Prints "OK <cases> cases <runs> runs <windows> windows".
  */
 #include "../../mindthegap_amd/csrc/mtg_profile_runs.h"
 #include <cstdio>
@@ -149,6 +152,37 @@ static void check(const std::vector<Seq>& seqs, bool junk, uint64_t cap_limit, c
     n_runs += total;
 }
 
+/* 3. one window of k bits from p.  The plane is a heap array of exactly the words the window touches */
+static unsigned long long n_windows = 0;
+static void check_covers_bad(const std::vector<uint64_t>& plane, uint32_t p, int k, const char* what)
+{
+    bool want = false;
+    for (uint32_t i = p; i < p + (uint32_t)k; i++) want = want || ((plane[i >> 6] >> (i & 63u)) & 1ull);
+    if (covers_bad(plane.data(), p, k) != want) { printf("FAIL (covers_bad, %s): k %d p %u expected %d\n", what, k, p, (int)want); exit(1); }
+    n_windows++;
+}
+static void covers_bad_cases()
+{
+    for (int k = 11; k <= 32; k++)
+        for (uint32_t p = 0; p <= 130; p++) {
+            const size_t nw = (size_t)((p + (uint32_t)k - 1u) >> 6) + 1; /* the word of the window's last bit is the last one */
+            std::vector<uint64_t> plane(nw);
+            for (int t = 0; t < 4; t++) {
+                for (uint64_t& x : plane) x = t < 2 ? rnd() : rnd() & rnd() & rnd() & rnd() & rnd(); /* dense, and sparse enough for clean windows */
+                check_covers_bad(plane, p, k, "random");
+            }
+            plane.assign(nw, 0ull);
+            check_covers_bad(plane, p, k, "all zero");
+            const int64_t at[4] = {(int64_t)p - 1, (int64_t)p, (int64_t)p + k - 1, (int64_t)p + k};
+            for (int64_t b : at) {
+                if (b < 0 || (size_t)(b >> 6) >= nw) continue; /* that bit lies outside the array */
+                plane.assign(nw, 0ull);
+                plane[(size_t)(b >> 6)] = 1ull << (b & 63);
+                check_covers_bad(plane, p, k, "one bit");
+            }
+        }
+}
+
 int main()
 {
     /* 1. every alignment of one run */
@@ -192,6 +226,7 @@ int main()
             const uint64_t caps[4] = {~0ull, 0, 1, want.size() ? want.size() - 1 : 0};
             check(seqs, t & 1, caps[t % 4], "random planes");
         }
-    printf("OK %llu cases %llu runs\n", n_cases, n_runs);
+    covers_bad_cases();
+    printf("OK %llu cases %llu runs %llu windows\n", n_cases, n_runs, n_windows);
     return 0;
 }

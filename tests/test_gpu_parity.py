@@ -276,6 +276,59 @@ def test_sequence_scan_bloom_kernel(mtg):
     _scan_case(mtg)
 
 
+def test_sequence_scan_of_packed_device_sequences(mtg):
+    """mtg_index_scan_packed_device (k_scan on the caller's device arrays, no upload) against mtg_index_scan_sequences on the same queries:
+    the bits of every position, exact and Bloom-only, the four statistics, and no word written outside a sequence's positions.  Lengths around
+    k and around the seams of the 64-bit result words and of the 256-position tile (63 / 64 / 65, 255 / 256 / 257 and 512 / 513 positions)"""
+    import torch
+    from tests import find_cases as fc
+    k = 31
+    rng = np.random.default_rng(31)
+    indexed = [fc.rand_seq(rng, 2100) for _ in range(20)]
+    kms = np.array(sorted(fc.solid_of_strings(indexed, k)), dtype=np.uint64)
+    g = mtg.Index.from_kmers(kms, np.full(len(kms), 9, dtype=np.uint32), k)
+    queries = []
+    for i, n in enumerate((30, 31, 32, 93, 94, 95, 285, 286, 287, 542, 543, 2000)):
+        if i % 2 == 0:
+            queries.append(fc.rand_seq(rng, n))
+        else:  # of the graph, every 97th character mutated
+            s = list(indexed[i][50:50 + n])
+            for p in range(20, n, 97):
+                s[p] = "ACGT"[("ACGT".index(s[p]) + 1) % 4]
+            queries.append("".join(s))
+    # the layout of mtg_index_create_from_packed_device, a sequence's words followed by two spare ones as the host entry lays them out
+    lens = np.array([len(s) for s in queries], dtype=np.uint32)
+    word_off = np.concatenate([[0], np.cumsum((lens.astype(np.int64) + 31) // 32 + 2)]).astype(np.uint64)
+    nwords = int(word_off[-1])
+    packed = np.zeros(nwords, dtype=np.uint64)
+    for s, o in zip(queries, word_off[:-1].tolist()):
+        codes = (np.frombuffer(s.encode(), dtype=np.uint8).astype(np.uint64) >> np.uint64(1)) & np.uint64(3)
+        np.bitwise_or.at(packed, o + np.arange(len(s)) // 32, codes << (np.uint64(2) * (np.arange(len(s), dtype=np.uint64) % np.uint64(32))))
+    dev = torch.device("cuda", 0)
+    d_w = torch.from_numpy(packed.view(np.int64)).to(dev)
+    d_wo = torch.from_numpy(word_off[:-1].copy().view(np.int64)).to(dev)
+    d_ln = torch.from_numpy(lens.view(np.int32)).to(dev)
+    untouched = np.uint64(0x5A5A5A5A5A5A5A5A)
+    for exact in (True, False):
+        per_pos, want_st = g.scan_sequences(queries, exact=exact)
+        want = np.full(nwords, untouched, dtype=np.uint64)
+        for s, o, b in zip(queries, word_off[:-1].tolist(), per_pos):
+            assert len(b) == max(len(s) - k + 1, 0)
+            nw = (len(b) + 63) // 64
+            want[o:o + nw] = 0
+            np.bitwise_or.at(want, o + np.arange(len(b)) // 64, b.astype(np.uint64) << (np.arange(len(b), dtype=np.uint64) % np.uint64(64)))
+        d_bits = torch.from_numpy(np.full(nwords, untouched, dtype=np.uint64).view(np.int64)).to(dev)
+        st = g.scan_packed_device(d_w.data_ptr(), d_wo.data_ptr(), d_ln.data_ptr(), len(queries), d_bits.data_ptr(), exact=exact)
+        torch.cuda.synchronize()
+        got = d_bits.cpu().numpy().view(np.uint64)
+        diff = np.flatnonzero(got != want)
+        assert len(diff) == 0, "exact=%r: word %d is %#x, expected %#x" % (exact, diff[0], int(got[diff[0]]), int(want[diff[0]]))
+        for name in ("n_kmers", "bloom_positive", "confirmed", "blocks_staged"):
+            assert st[name] == want_st[name], (exact, name, st[name], want_st[name])
+        assert st["n_kmers"] == sum(max(len(s) - k + 1, 0) for s in queries) and 0 < st["bloom_positive"] < st["n_kmers"]
+    g.close()
+
+
 def test_contig_mode_many_targets(mtg, tmp_path):
     """400 contigs / 800 seeds / ~800 anchors per seed: exercises the multi-target terminal search of k_post"""
     from tests.test_emu_parity import _contig_gap_case

@@ -1,6 +1,6 @@
 """The sequence profile (include/mtg_fill.h: mtg_index_profile_sequences) without a GPU: the product exports it and the Python names import,
-the tool refuses to run without a device and leaves no files, and the run extraction the kernels share with tests/emu/profile_runs.cpp equals
-a literal loop over positions (also under AddressSanitizer + UBSan, as a program of its own)."""
+the tool refuses to run without a device and leaves no files, and the run extraction and the bad-bit test the kernels share with
+tests/emu/profile_runs.cpp equal literal loops (also under AddressSanitizer + UBSan, as a program of its own)."""
 import ctypes as C
 import os
 import subprocess
@@ -71,6 +71,7 @@ def test_run_extraction_equals_the_literal_loop(tmp_path):
     """mtg_profile_runs.h by g++: every alignment of a run against the 64-bit and the 256-position seams, random planes of 0 .. 1100 positions"""
     out = _build_and_run(tmp_path, "profile_runs", ["-O2"])
     assert int(out.split()[1]) > 100000 and int(out.split()[3]) > 100000
+    assert int(out.split()[5]) > 22 * 131 * 7  # covers_bad: 22 values of k, 131 of p, four random planes, the zero plane, two to four single bits
 
 
 def test_run_extraction_under_sanitizers(tmp_path):
