@@ -854,7 +854,7 @@ static int run_bkpt(const Replicas& R, const mtg_params& P, const Options& O, Fi
             if (text.capacity()) text_pool().put(std::move(text));
         }
     };
-    enum { FORMAT_CHUNK = 2048 };
+    enum { FORMAT_CHUNK = 2048, REV_EMPTY = -2 };
     /* MTG_TOOL_TIMERS=1: where the time of a run goes (summed over the worker threads; read and write are one thread each) */
     const bool timers = tune::on(tune::T_TOOL_TIMERS);
     std::atomic<long long> t_read{0}, t_parse{0}, t_fill{0}, t_rev{0}, t_format{0}, t_write{0};
@@ -917,8 +917,12 @@ static int run_bkpt(const Replicas& R, const mtg_params& P, const Options& O, Fi
         /* reverse attempt for the sites without solution, src/Filler.cpp:669-680 */
         bt.rev_idx.assign(n, -1);
         if (!O.fwd_only) {
+            /* revcomp_sequence drops what is not a nucleotide: the reverse source of a right k-mer with an N has fewer than k characters, no walk starts
+             * from it and the attempt comes back empty (REV_EMPTY: it is not sent to the library, which refuses such a source) */
+            const auto nucleotides = [](const BkptRec& r) { size_t c = 0; for (uint32_t i = 0; i < r.seq_len; i++) { const char u = (char)(r.seq[i] & 0xDF); c += (u == 'A' || u == 'C' || u == 'G' || u == 'T'); } return c; };
             size_t nr = 0;
-            for (size_t j = 0; j < n; j++) if (mtg_results_get(bt.rf, j)->n_filled == 0) bt.rev_idx[j] = (long)nr++;
+            for (size_t j = 0; j < n; j++)
+                if (mtg_results_get(bt.rf, j)->n_filled == 0) bt.rev_idx[j] = nucleotides(bt.recs[2 * j + 1]) < (size_t)idx->info.k ? (long)REV_EMPTY : (long)nr++;
             bt.rev.resize(nr);
             size_t q = 0;
             for (size_t j = 0; j < n && nr; j++)
@@ -943,6 +947,8 @@ static int run_bkpt(const Replicas& R, const mtg_params& P, const Options& O, Fi
             }
         }
         t_rev += usec() - tp; tp = usec();
+        static const mtg_gap_result no_walk = [] { mtg_gap_result g{}; g.extension = ""; return g; }();
+        const auto rev_of = [&](size_t j) -> const mtg_gap_result* { return bt.rev_idx[j] >= 0 ? mtg_results_get(bt.rr, (size_t)bt.rev_idx[j]) : bt.rev_idx[j] == (long)REV_EMPTY ? &no_walk : nullptr; };
         if (bt.ftext) {
             /* the device has written the simple sites; the host's writers take the others (reverse attempts, several solutions, records the host
              * wrote), one small piece per site, placed between the device's bytes when the batch is consumed */
@@ -959,7 +965,7 @@ static int run_bkpt(const Replicas& R, const mtg_params& P, const Options& O, Fi
                     T = piece_pool().get();
                     const BkptRec &l = bt.recs[2 * j], &r = bt.recs[2 * j + 1];
                     const SiteRef site{std::string_view(l.hdr, bt.name_len[j]), std::string_view(r.hdr, bt.name_r_len[j]), std::string_view(l.seq, l.seq_len), std::string_view(r.seq, r.seq_len)};
-                    const size_t nsol = format_bkpt_site(T, site, mtg_results_get(bt.rf, j), bt.rev_idx[j] >= 0 ? mtg_results_get(bt.rr, (size_t)bt.rev_idx[j]) : nullptr, O.filter, O.extend, info);
+                    const size_t nsol = format_bkpt_site(T, site, mtg_results_get(bt.rf, j), rev_of(j), O.filter, O.extend, info);
                     pf[q] = nsol > 0; pm[q] = nsol > 1;
                 }
             }, 1);
@@ -980,7 +986,7 @@ static int run_bkpt(const Replicas& R, const mtg_params& P, const Options& O, Fi
             for (size_t j = pc * FORMAT_CHUNK; j < j1; j++) {
                 const BkptRec &l = bt.recs[2 * j], &r = bt.recs[2 * j + 1];
                 const SiteRef site{std::string_view(l.hdr, bt.name_len[j]), std::string_view(r.hdr, bt.name_r_len[j]), std::string_view(l.seq, l.seq_len), std::string_view(r.seq, r.seq_len)};
-                const size_t nsol = format_bkpt_site(T, site, mtg_results_get(bt.rf, j), bt.rev_idx[j] >= 0 ? mtg_results_get(bt.rr, (size_t)bt.rev_idx[j]) : nullptr, O.filter, O.extend, info);
+                const size_t nsol = format_bkpt_site(T, site, mtg_results_get(bt.rf, j), rev_of(j), O.filter, O.extend, info);
                 pf[pc] += nsol > 0;
                 pm[pc] += nsol > 1;
             }

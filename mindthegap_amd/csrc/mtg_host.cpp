@@ -914,15 +914,17 @@ static int run_general(const mtg_index* idx, const mtg_params* p, const DevBatch
         set_error("a multi-contig gap could not be taken from the device's answer, and its contigs are not on the host");
         return MTG_ERR_FORMAT;
     }
-    if (!check_of.empty()) {
-        DevBatch sub; /* the same gaps as a batch of their own with the device's answers hidden: run_general's host path, whole */
-        for (size_t i : check_of) {
+    /* launch by launch (a batch at low k takes several): the checked gaps of one launch are a batch of their own that borrows that launch's chunk */
+    while (!check_of.empty()) {
+        const uint32_t ch0 = special.special[check_of[0]].chunk;
+        std::vector<size_t> of_launch, later;
+        for (size_t i : check_of) (special.special[i].chunk == ch0 ? of_launch : later).push_back(i);
+        check_of.swap(later);
+        DevBatch sub; /* the same gaps with the device's answers hidden: run_general's host path, whole */
+        for (size_t i : of_launch) {
             const SpecialGap& sg = special.special[i];
             sub.special.push_back(SpecialGap{sg.gap, 0, sg.slot, ~0u});
         }
-        /* one chunk per source chunk would need re-indexing; the emulation's batches of this kind come from one launch: check that and borrow it */
-        const uint32_t ch0 = special.special[check_of[0]].chunk;
-        for (size_t i : check_of) if (special.special[i].chunk != ch0) { set_error("general-path cross-check: gaps of several launches"); return MTG_ERR_OVERFLOW; }
         HostChunk* borrowed = special.chunks[ch0].get();
         sub.chunks.emplace_back(borrowed);
         struct Unborrow { DevBatch& b; ~Unborrow() { (void)b.chunks[0].release(); } } unborrow{sub};
@@ -934,16 +936,16 @@ static int run_general(const mtg_index* idx, const mtg_params* p, const DevBatch
         hidden.swap(borrowed->gen_gaps);
         borrowed->gen_check = saved;
         if (crc) return crc;
-        for (size_t q = 0; q < check_of.size(); q++) {
-            if (!on_device[check_of[q]]) continue; /* the host could not take this gap from the device's answer (two targets under one name): its own path is what runs, below */
-            const GapWork& a = work[check_of[q]];
+        for (size_t q = 0; q < of_launch.size(); q++) {
+            if (!on_device[of_launch[q]]) continue; /* the host could not take this gap from the device's answer (two targets under one name): its own path is what runs, below */
+            const GapWork& a = work[of_launch[q]];
             const GapWork& b = check[q];
             bool same = a.sols.size() == b.sols.size() && a.nb_total_filled == b.nb_total_filled && a.has_counts == b.has_counts;
             for (size_t j = 0; same && j < a.sols.size(); j++) {
                 const Solution &x = a.sols[j], &y = b.sols[j];
                 same = x.seq == y.seq && x.nb_errors == y.nb_errors && x.target == y.target && x.avg == y.avg && x.median == y.median && x.qual == y.qual && x.count == y.count && x.rank == y.rank;
             }
-            if (!same) { set_error("gap %u: the device's multi-contig path (mtg_general.h) and the host's disagree", special.special[check_of[q]].gap); return MTG_ERR_OVERFLOW; }
+            if (!same) { set_error("gap %u: the device's multi-contig path (mtg_general.h) and the host's disagree", special.special[of_launch[q]].gap); return MTG_ERR_OVERFLOW; }
         }
     }
     /* every alignment remove_almost_identical_solutions can ask for: a later candidate (rows) against an earlier one (columns) */

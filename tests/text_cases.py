@@ -34,17 +34,18 @@ def text_vs_strings(mtg, idx, gaps):
     return a
 
 
-def run(mtg, oracle_lib):
+def run(mtg, oracle_lib, k=31, check=None):
     """mtg_fill_text (strings as offsets into one block, encoded by k_marshal_text / k_marshal_targets -- here their per-gap functions on the
     host) against mtg_fill_batch on the same strings, including the ones the marshalling treats specially: lower case, N in source / pattern /
     dictionary key, a source longer than k, keys shorter and longer than k, a pattern shorter than k, empty dictionaries, several entries,
-    repeated anchors and reverse attempts"""
+    repeated anchors and reverse attempts.  The places of the N and of the cut are expressions of k (10, 5, 20 and 15 at k = 31).
+    check(S, o, gaps, res), when given, sees every set, its oracle index, the gaps and the records both entries agreed on."""
     from mindthegap_amd.synth import SynthSet
     for het in (0, 4):
-        S = SynthSet(nseq=60 if not het else 80, n_sites=40, seed=11, het_snps=het)
-        o = oracle_lib.Index.from_sequences([S.ascii(j) for j in range(S.nseq)], 31, 3, 40)
+        S = SynthSet(nseq=60 if not het else 80, n_sites=40, seed=11, het_snps=het, k=k)
+        o = oracle_lib.Index.from_sequences([S.ascii(j) for j in range(S.nseq)], k, 3, 40)
         km, ct = o.export()
-        idx = mtg.Index.from_kmers(km, ct, 31)
+        idx = mtg.Index.from_kmers(km, ct, k)
         gaps = []
         for i in range(S.n_sites):
             l, r, _ = S.site(i)
@@ -53,13 +54,13 @@ def run(mtg, oracle_lib):
             if v == 0:
                 gaps.append(mtg.Gap(l.lower(), r, [(r.lower(), name, False)]))
             elif v == 1:
-                gaps.append(mtg.Gap(l, r[:10] + "N" + r[11:], [(r, name, False)]))          # pattern with N: never stops early
+                gaps.append(mtg.Gap(l, r[:k // 3] + "N" + r[k // 3 + 1:], [(r, name, False)]))          # pattern with N: never stops early
             elif v == 2:
-                gaps.append(mtg.Gap(l, r, [(r[:5] + "N" + r[6:], name, False), (r, name + "_b", True)]))
+                gaps.append(mtg.Gap(l, r, [(r[:k // 6] + "N" + r[k // 6 + 1:], name, False), (r, name + "_b", True)]))
             elif v == 3:
                 gaps.append(mtg.Gap(l + "ACGT", r, [(r + "TTGA", name, False)]))            # longer than k: the first k characters count
             elif v == 4:
-                gaps.append(mtg.Gap(l, r[:20], [(r[:20], name, False)]))                    # shorter than k: unusable key, short pattern
+                gaps.append(mtg.Gap(l, r[:2 * k // 3], [(r[:2 * k // 3], name, False)]))                    # shorter than k: unusable key, short pattern
             elif v == 5:
                 gaps.append(mtg.Gap(l, r, []))
             elif v == 6:
@@ -67,24 +68,27 @@ def run(mtg, oracle_lib):
             elif v == 7:
                 gaps.append(mtg.Gap(_rc(r), _rc(l), [(_rc(l), name, True)], reverse=True))
             elif v == 8:
-                gaps.append(mtg.Gap(l[:15] + "N" + l[16:], r, [(r, name, False)]))          # N in the source: not the fast form
+                gaps.append(mtg.Gap(l[:k // 2] + "N" + l[k // 2 + 1:], r, [(r, name, False)]))          # N in the source: not the fast form
             else:
                 gaps.append(mtg.Gap(l, r, [(r, name, False)]))
         res = text_vs_strings(mtg, idx, gaps)
         assert sum(1 for r in res if r["filled"]) >= 10
+        if check is not None:
+            check(S, o, gaps, res)
         idx.close()
+        o.close()
     # malformed batches are refused, not read
     from mindthegap_amd import lib as L
-    S = SynthSet(nseq=20, n_sites=4, seed=2)
-    o = oracle_lib.Index.from_sequences([S.ascii(j) for j in range(S.nseq)], 31, 3, 40)
+    S = SynthSet(nseq=20, n_sites=4, seed=2, k=k)
+    o = oracle_lib.Index.from_sequences([S.ascii(j) for j in range(S.nseq)], k, 3, 40)
     km, ct = o.export()
-    idx = mtg.Index.from_kmers(km, ct, 31)
+    idx = mtg.Index.from_kmers(km, ct, k)
     l, r, _ = S.site(0)
     tg = mtg.TextGaps([mtg.Gap(l, r, [(r, "x", False)])])
     tg.arrays["pattern_off"][0] = len(tg.text) + 5
     with pytest.raises(L.MtgError):
         idx.fill_prepared(tg)
-    tg = mtg.TextGaps([mtg.Gap(l[:20], r, [(r, "x", False)])])
+    tg = mtg.TextGaps([mtg.Gap(l[:2 * k // 3], r, [(r, "x", False)])])
     with pytest.raises(L.MtgError):
         idx.fill_prepared(tg)
     idx.close()
