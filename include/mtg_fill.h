@@ -201,6 +201,29 @@ int mtg_index_find_het_sequences(const mtg_index* idx, const char* const* seqs, 
 int mtg_index_find_het_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, const uint64_t* d_repeat_bits,
                                      int max_repeat, int branching_filter, mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_het_stats* st);
 
+/* `find` for homozygous deletions: the reference's gap observer FindDeletion (src/FindDeletion.hpp:58-188) and no other, on the gaps of
+ * mtg_index_find_homo_sequences.  A reported gap of L >= k - max_repeat positions (no upper bound) with a valid k-mer right before it (begin,
+ * at left) and the k-mer right behind it (end, at right = left + 1 + L): r = the largest i in max_repeat .. 1 with the last i nucleotides of
+ * begin equal to the first i of end, else 0.  When every k-mer of begin[0 : k - r] + end is in the graph it is a deletion of
+ * del_size = L - k + r + 1 nucleotides; else, with r > 0, when every k-mer of begin + end is: a deletion of L - k + 1 with r = 0 (counted in
+ * n_fallback); del_size <= 0 is no deletion.  The observer reads no history and does not change the scan.  Records as above:
+ *   kind   4 deletion
+ *   pos    0-based position of the nucleotide before the deleted text (left + k - 1 - r; the VCF's POS is pos + 1);  repeat = r
+ *   left, right   positions of the two k-mers;  ins = del_size
+ * in the order of the scan (ascending seq, then right).  In a combined run the reference asks this observer first: a gap it calls is not
+ * seen by the insertion observers (the tool drops their calls with the same (seq, left)).  max_repeat, cap, *n_calls, calls, st and the
+ * character rule as for mtg_index_find_homo_sequences. */
+typedef struct mtg_find_del_stats {
+    uint64_t n_positions, n_gaps /* calls of the gap observers */, n_candidates /* of those, both k-mers valid and L >= k - max_repeat */;
+    uint64_t n_del_clean, n_del_fuzzy /* deletions called, r = 0 / r > 0 */, n_fallback /* begin + end held after the shorter text failed */, n_calls;
+    double kernel_ms;
+} mtg_find_del_stats;
+int mtg_index_find_del_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls,
+                                 mtg_find_del_stats* st);
+/* same on 2-bit packed sequences already in DEVICE memory (no invalid positions); d_calls is a device array */
+int mtg_index_find_del_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
+                                     mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_del_stats* st);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Gap filling = Filler::gapFillFromSource over a batch of gaps.
  * ---------------------------------------------------------------------------------------------------------- */
@@ -478,13 +501,17 @@ int mtg_fill_main_on_index(mtg_index* idx, int argc, const char* const* argv);
  * name, start, start + length, length, L|R|LR|. (k-mer start positions, 0-based, half-open; name = the FASTA header up to the first blank),
  * and prefix.profile.txt, the statistics as `key : value` lines.  Returns 0 / 1; nothing is written unless the whole profile succeeded. */
 int mtg_profile_main(int argc, const char* const* argv);
-/* `MindTheGap find (-in reads | -graph container) -ref genome.fa (-homo-insertions | -hete-only | -insert-only) [-max-rep 5] [-het-max-occ 1]
- * [-branching-filter 15] [-kmer-size -abundance-min -abundance-max] [-out prefix]`: the part of the reference's `find` that
- * mtg_index_find_homo_sequences (-homo-insertions), mtg_index_find_het_sequences plus the homozygous insertions of 1-2 nt (-hete-only, as the
- * reference's option of that name) or both in full (-insert-only, calls merged in detection order) cover.  The repeat flags of the heterozygous
- * observer come from an index of the genome file at k - 1 with abundance_min = het_max_occ + 1 (k >= 12).  Without one of the three flags it stops
- * with a message that names what is not built (SNPs, deletions, -bed) and returns 1.  Writes prefix.breakpoints (writeBreakpoint,
- * src/FindBreakpoints.hpp:640-658) and prefix.othervariants.vcf (header of src/Finder.cpp:513-541, records of writeIndel); ids bkptN count
+/* `MindTheGap find (-in reads | -graph container) -ref genome.fa (-homo-insertions | -hete-only | -insert-only | -deletion-only | -homo-only
+ * -no-snp | -no-snp) [-max-rep 5] [-het-max-occ 1] [-branching-filter 15] [-kmer-size -abundance-min -abundance-max] [-out prefix]`: the part
+ * of the reference's `find` that mtg_index_find_homo_sequences (-homo-insertions), mtg_index_find_het_sequences plus the homozygous insertions
+ * of 1-2 nt (-hete-only, as the reference's option of that name) or both in full (-insert-only, calls merged in detection order) cover, and with
+ * mtg_index_find_del_sequences the reference's -deletion-only (deletions and the homozygous insertions of 1-2 nt), -homo-only -no-snp (those and
+ * the homozygous sites) and -no-snp (all three layers: its default find minus the SNP observers); an insertion call on a gap that the deletion
+ * observer calls is dropped, as the reference asks that observer first.  The repeat flags of the heterozygous
+ * observer come from an index of the genome file at k - 1 with abundance_min = het_max_occ + 1 (k >= 12).  Any other combination of these flags
+ * stops with a message that names what is not built (SNPs, -bed) and returns 1.  Writes prefix.breakpoints (writeBreakpoint,
+ * src/FindBreakpoints.hpp:640-658) and prefix.othervariants.vcf (header of src/Finder.cpp:513-541, records of writeIndel and, for deletions,
+ * writeVcfVariant: REF = the genome's text from pos over del_size + 1 characters as it stands, ALT its first); ids bkptN count
  * from 1 in detection order across both files; the REPEATED field stays empty (the reference fills it from a Bloom filter of the genome's
  * (k-1)-mers, whose false positives are not reproducible).  Prints the Results block of the reference's summary.  Returns 0 / 1; nothing is
  * written unless the whole scan succeeded. */

@@ -1448,13 +1448,15 @@ int profile_main(int argc, const char* const* argv)
 
 /* `MindTheGap find -homo-insertions | -hete-only | -insert-only`: the insertion sites and the insertions of 1-2 nt of a reference genome against
  * the graph, homozygous (mtg_index_find_homo_sequences), heterozygous (mtg_index_find_het_sequences) or both, in the reference's two files.
- * Both are written once the whole scan is there. */
+ * `-deletion-only | -homo-only -no-snp | -no-snp`: the reference's configurations of those names (src/Finder.cpp:320-398, :549-582), with the
+ * homozygous deletions of mtg_index_find_del_sequences ahead of the insertion observers.  Both files are written once the whole scan is there. */
 int find_main(int argc, const char* const* argv)
 {
     std::string in, graph, ref, out = "MindTheGap_Expe"; /* the reference names it after the date (src/Finder.cpp: MindTheGap_Expe-<date>) */
     int k = 31, abundance_min = -1, abundance_max = 0, max_repeat = 5, het_max_occ = 1, branching_filter = 15;
-    bool homo_flag = false, hete_only = false, insert_only = false;
-    const char* usage = "Usage: MindTheGap find (-in <reads> | -graph <container>) -ref <genome.fa> (-homo-insertions | -hete-only | -insert-only) [-max-rep 5] [-het-max-occ 1] "
+    bool homo_flag = false, hete_only = false, insert_only = false, deletion_only = false, homo_only = false, no_snp = false, other_mode = false;
+    const char* usage = "Usage: MindTheGap find (-in <reads> | -graph <container>) -ref <genome.fa> (-homo-insertions | -hete-only | -insert-only | -deletion-only | -homo-only -no-snp | "
+                        "-no-snp) [-max-rep 5] [-het-max-occ 1] "
                         "[-branching-filter 15] [-kmer-size 31] [-abundance-min auto] [-abundance-max 0] [-out <prefix>]\n";
     for (int i = 0; i < argc; i++) {
         const std::string a = argv[i];
@@ -1468,6 +1470,10 @@ int find_main(int argc, const char* const* argv)
         else if (a == "-homo-insertions") homo_flag = true;
         else if (a == "-hete-only") hete_only = true;
         else if (a == "-insert-only") insert_only = true;
+        else if (a == "-deletion-only") deletion_only = true;
+        else if (a == "-homo-only") homo_only = true;
+        else if (a == "-no-snp") no_snp = true;
+        else if (a == "-snp-only" || a == "-no-insert" || a == "-no-deletion" || a == "-no-hetero" || a == "-with-backup") other_mode = true; /* refused below, with the message */
         else if (a == "-het-max-occ") { ok = val(v); het_max_occ = atoi(v.c_str()); }
         else if (a == "-branching-filter") { ok = val(v); branching_filter = atoi(v.c_str()); }
         else if (a == "-max-rep") { ok = val(v); max_repeat = atoi(v.c_str()); }
@@ -1483,11 +1489,17 @@ int find_main(int argc, const char* const* argv)
     /* -hete-only keeps the two observers of homozygous insertions of 1-2 nt, as the reference's option of that name does (_small_homo stays true,
      * src/Finder.cpp:364-373,562-566): the gap layer runs and its sites are left out.  A gap goes to the site observers only when the small ones
      * did not call it, so the calls of 1-2 nt are the same with and without them */
-    const bool run_homo = homo_flag || insert_only || hete_only, run_het = hete_only || insert_only, homo_sites = homo_flag || insert_only;
-    if (!run_homo && !run_het) {
-        fprintf(stderr, "EXCEPTION: this build of find detects insertions only (sites and insertions of 1-2 nt): SNPs, deletions and -bed are not built, and heterozygous "
-                        "insertions are found only under -hete-only or -insert-only.  Pass -homo-insertions, -hete-only or -insert-only to run that subset; only -insert-only "
-                        "is a configuration of the reference, none of them is its default find.\n%s", usage);
+    /* The insertion flags as they were, or one configuration with the deletion observer: -deletion-only (that observer and the small ones), or
+     * -no-snp with or without -homo-only (those and the site observers; the heterozygous observer without -homo-only).  Nothing else */
+    const bool ins_flags = homo_flag || hete_only || insert_only, del_flags = deletion_only || homo_only || no_snp;
+    const bool run_del = !other_mode && !ins_flags && (no_snp ? !deletion_only : deletion_only && !homo_only);
+    const bool known = run_del || (!other_mode && ins_flags && !del_flags);
+    const bool run_homo = known, run_het = known && (hete_only || insert_only || (no_snp && !homo_only)), homo_sites = known && (homo_flag || insert_only || no_snp);
+    if (!known) {
+        fprintf(stderr, "EXCEPTION: this build of find detects insertions (sites and insertions of 1-2 nt) and homozygous deletions: SNPs and -bed are not built, deletions are "
+                        "found only under -deletion-only, -homo-only -no-snp or -no-snp, and heterozygous insertions only under -hete-only, -insert-only or -no-snp.  Pass "
+                        "-homo-insertions, -hete-only, -insert-only, -deletion-only, -homo-only -no-snp or -no-snp; all but -homo-insertions are configurations "
+                        "of the reference, none of them is its default find, which looks for SNPs too.\n%s", usage);
         return 1;
     }
     if (graph.empty() == in.empty()) { fprintf(stderr, "EXCEPTION: options -graph and -in are incompatible, but at least one of these is mandatory\n"); return 1; }
@@ -1504,8 +1516,8 @@ int find_main(int argc, const char* const* argv)
     if (rc) { fprintf(stderr, "EXCEPTION: %s\n", mtg_last_error()); return 1; }
     std::vector<const char*> seqs(recs.size());
     for (size_t i = 0; i < recs.size(); i++) seqs[i] = recs[i].second.c_str();
-    std::vector<mtg_find_call> calls(run_homo ? 4096 : 0), het_calls(run_het ? 4096 : 0);
-    size_t n_calls = 0, n_het = 0;
+    std::vector<mtg_find_call> calls(run_homo ? 4096 : 0), het_calls(run_het ? 4096 : 0), del_calls(run_del ? 4096 : 0);
+    size_t n_calls = 0, n_het = 0, n_del = 0;
     mtg_find_stats st{};
     mtg_find_het_stats hst{};
     const time_t t_start = time(0);
@@ -1523,6 +1535,14 @@ int find_main(int argc, const char* const* argv)
             n_calls = (size_t)(std::remove_if(calls.begin(), calls.begin() + (ptrdiff_t)n_calls, [](const mtg_find_call& c) { return c.kind == 0; }) - calls.begin());
             st.n_homo_clean = st.n_homo_fuzzy = 0;
         }
+    }
+    if (run_del && !rc) {
+        rc = mtg_index_find_del_sequences(idx, seqs.data(), seqs.size(), max_repeat, del_calls.data(), del_calls.size(), &n_del, nullptr);
+        if (!rc && n_del > del_calls.size()) {
+            del_calls.resize(n_del);
+            rc = mtg_index_find_del_sequences(idx, seqs.data(), seqs.size(), max_repeat, del_calls.data(), del_calls.size(), &n_del, nullptr);
+        }
+        if (!rc && n_del > del_calls.size()) { rc = MTG_ERR_ARG; set_error("the number of calls changed between two calls"); }
     }
     if (run_het && !rc) {
         /* the repeated (k-1)-mers of the genome (fillRefBloom, src/FindBreakpoints.hpp:956-1008, as an exact set): an index of the genome file at
@@ -1551,12 +1571,33 @@ int find_main(int argc, const char* const* argv)
     const double seconds = difftime(time(0), t_start);
     mtg_index_free(idx);
     if (rc) { fprintf(stderr, "EXCEPTION: %s\n", mtg_last_error()); return 1; }
+    if (run_del) {
+        /* the reference asks the deletion observer first and leaves the gap at the first observer that calls it (src/FindBreakpoints.hpp:582-590):
+         * an insertion call on a gap with a deletion call -- the same (seq, left) -- is dropped.  Both lists are in scan order; a deletion is
+         * detected where a homozygous insertion is (right - repeat + 1 there, right + 1 here), and no gap keeps two calls, so the merge by
+         * that position is the order of detection.  The counts of the summary are those of the merged list */
+        std::vector<mtg_find_call> all;
+        all.reserve(n_calls + n_del);
+        size_t i = 0, j = 0;
+        while (i < n_calls || j < n_del) {
+            if (i < n_calls && j < n_del && calls[i].seq == del_calls[j].seq && calls[i].left == del_calls[j].left) { i++; continue; }
+            const bool del_first = j < n_del && (i >= n_calls || (del_calls[j].seq != calls[i].seq ? del_calls[j].seq < calls[i].seq : del_calls[j].right + 1u < calls[i].right - calls[i].repeat + 1u));
+            all.push_back(del_first ? del_calls[j++] : calls[i++]);
+        }
+        calls.swap(all);
+        n_calls = calls.size();
+        st.n_homo_clean = st.n_homo_fuzzy = st.n_small_clean = st.n_small_fuzzy = 0;
+        for (const mtg_find_call& c : calls) {
+            if (c.kind == 0) (c.repeat ? st.n_homo_fuzzy : st.n_homo_clean)++;
+            else if (c.kind == 1) (c.repeat ? st.n_small_fuzzy : st.n_small_clean)++;
+        }
+    }
     if (run_het) {
         /* both lists are in scan order; merged in the order of detection: a heterozygous call is made at position right - repeat, a homozygous one
          * at right - repeat + 1, and at one position the k-mer observers run before the gap observers (src/FindBreakpoints.hpp:566-590) */
         std::vector<mtg_find_call> all(n_calls + n_het);
         const auto before = [](const mtg_find_call& a, const mtg_find_call& b) { /* a heterozygous, b homozygous */
-            return a.seq != b.seq ? a.seq < b.seq : a.right - a.repeat <= b.right - b.repeat + 1u;
+            return a.seq != b.seq ? a.seq < b.seq : a.right - a.repeat <= (b.kind == 4 ? b.right : b.right - b.repeat) + 1u;
         };
         size_t i = 0, j = 0, o = 0;
         while (i < n_calls || j < n_het) all[o++] = (j < n_het && (i >= n_calls || before(het_calls[j], calls[i]))) ? het_calls[j++] : calls[i++];
@@ -1583,8 +1624,11 @@ int find_main(int argc, const char* const* argv)
         const std::string name = h.substr(0, h.find_first_of(" \t")), &s = recs[c.seq].second;
         const std::string left = kmer_string(s, c.left);
         const int id = (int)i + 1;
-        const bool het = c.kind >= 2;
-        if (c.kind == 0 || c.kind == 2) { /* writeBreakpoint, src/FindBreakpoints.hpp:640-658; the fuzzy right k-mer is the genome's text as it stands (FindInsertion.hpp:114), and so
+        const bool het = c.kind == 2 || c.kind == 3;
+        if (c.kind == 4) { /* writeVcfVariant, :661-678, as FindDeletion.hpp:148-160 calls it: the genome's text as it stands */
+            const std::string del = s.substr(c.pos, (size_t)c.ins + 1);
+            appendf(vcf, "%s\t%lli\tbkpt%i\t%s\t%c\t.\tPASS\tTYPE=DEL;LEN=%i;FUZZY=%i\tGT\t1/1\n", name.c_str(), (long long)c.pos + 1, id, del.c_str(), del[0], (int)c.ins, (int)c.repeat);
+        } else if (c.kind == 0 || c.kind == 2) { /* writeBreakpoint, src/FindBreakpoints.hpp:640-658; the fuzzy right k-mer is the genome's text as it stands (FindInsertion.hpp:114), and so
                                              is every right k-mer of the heterozygous observer (FindHeteroInsertion.hpp:76) */
             const std::string right = (c.repeat || het) ? s.substr(c.right, (size_t)k) : kmer_string(s, c.right);
             const char* type = het ? "HET" : "HOM";
@@ -1608,12 +1652,14 @@ int find_main(int argc, const char* const* argv)
     printf("    Breakpoint detection options\n        max_repeat                               : %i\n", max_repeat);
     if (run_het) printf("        hetero_max_occ                           : %i\n        branching filter value                   : %i\n", het_max_occ, branching_filter);
     printf("        homo_insertions                          : %s\n        hete_insertions                          : %s\n        snp                                      : no\n"
-           "        deletion                                 : no\n", homo_sites ? "yes" : "no", run_het ? "yes" : "no");
+           "        deletion                                 : %s\n", homo_sites ? "yes" : "no", run_het ? "yes" : "no", run_del ? "yes" : "no");
     printf("Results\n    Insertion breakpoints\n        homozygous                               : %llu\n            clean                                    : %llu\n"
            "            fuzzy                                    : %llu\n", (unsigned long long)(st.n_homo_clean + st.n_homo_fuzzy), (unsigned long long)st.n_homo_clean, (unsigned long long)st.n_homo_fuzzy);
     if (run_het) printf("        heterozygous                             : %llu\n            clean                                    : %llu\n            fuzzy                                    : %llu\n",
                         (unsigned long long)(hst.n_het_clean + hst.n_het_fuzzy), (unsigned long long)hst.n_het_clean, (unsigned long long)hst.n_het_fuzzy);
-    printf("    Other variants\n        Homozygous insertions 1-2 bp size        : %llu\n", (unsigned long long)(st.n_small_clean + st.n_small_fuzzy));
+    printf("    Other variants\n");
+    if (run_del) printf("        deletions                                : %llu\n", (unsigned long long)n_del);
+    printf("        Homozygous insertions 1-2 bp size        : %llu\n", (unsigned long long)(st.n_small_clean + st.n_small_fuzzy));
     if (run_het) printf("        Heterozygous insertions 1-2 bp size      : %llu\n", (unsigned long long)hst.n_het_small);
     printf("    Time                                     : %.1f s\n    Output files\n        breakpoint_file                          : %s.breakpoints\n        othervariants_file                       : %s.othervariants.vcf\n",
            seconds, out.c_str(), out.c_str());

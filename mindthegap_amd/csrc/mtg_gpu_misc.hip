@@ -16,6 +16,7 @@
 #include "mtg_profile_runs.h"
 #include "mtg_find_gaps.h"
 #include "mtg_find_het.h"
+#include "mtg_find_del.h"
 
 namespace mtgi {
 
@@ -321,6 +322,7 @@ __global__ void __launch_bounds__(SCAN_TILE) k_scan(Index ix, const uint64_t* __
 enum { CNT_POSITIONS, CNT_VALID, CNT_PRESENT, CNT_PROFILE };
 enum { CNT_RUNS = 4, CNT_RUNS_LONGEST, CNT_PROFILE_SLOTS = 8 };
 enum { CNT_GAPS = 4, CNT_GAPS_LONGEST, CNT_HOMO_CANDIDATES, CNT_HOMO_CALLS, CNT_GAPS_SEEN, CNT_HOMO_CLEAN = 10, CNT_HOMO_FUZZY, CNT_SMALL_CLEAN, CNT_SMALL_FUZZY, CNT_HOMO_SLOTS = 16 };
+enum { CNT_DEL_CANDIDATES = 6, CNT_DEL_CALLS, CNT_DEL_GAPS_SEEN, CNT_DEL_CLEAN = 10, CNT_DEL_FUZZY, CNT_DEL_FALLBACK, CNT_DEL_SLOTS = 16 }; /* (CNT_GAPS, CNT_GAPS_LONGEST as above) */
 enum { CNT_HET_LISTED = 4, CNT_HET_CALLS = 6, CNT_HET_CANDIDATES = 8, CNT_HET_RAW_SITES, CNT_HET_FILTERED, CNT_HET_SUPPRESSED, CNT_HET_CLEAN, CNT_HET_FUZZY, CNT_HET_SMALL, CNT_HET_SLOTS = 16 };
 
 /* profile along packed sequences: the tile of k_scan (scan_tile_stage: the tile's m-mers hashed once in LDS, Bloom blocks staged by coalesced
@@ -614,6 +616,75 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_find_emit(const mtg_run* __restr
     const uint32_t e = g.start + g.length, r = (uint32_t)(k - 1) - g.length, kind = (o >> 1) & 1u;
     mtg_find_call q;
     q.seq = g.seq; q.pos = kind ? e - 1u : e - 1u + r; q.kind = kind; q.repeat = r; q.left = g.start - 1u; q.right = e + r; q.ins = o >> 8;
+    calls[j] = q;
+}
+
+/* ---- `find` for homozygous deletions (include/mtg_fill.h: mtg_index_find_del_sequences; the rule: mtg_find_del.h).  The gaps are those of the
+ * insertion observers (k_profile_count<true> / k_profile_write<true>), the candidates and the calls are listed by k_mark_*.
+ * k_del_mark: one thread per gap, the candidate test alone; CNT_DEL_GAPS_SEEN += gaps the observers see. */
+__global__ void __launch_bounds__(RUNS_BLOCK) k_del_mark(const mtg_run* __restrict__ gaps, uint64_t n, int k, int max_repeat, uint32_t* mark, unsigned long long* counters)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    bool seen = false;
+    if (i < n) {
+        const mtg_run g = gaps[i];
+        seen = (g.flags & 2u) != 0;
+        mark[i] = gap_is_del_candidate(g.length, g.flags, k, max_repeat) ? 1u : 0u;
+    }
+    const unsigned long long bal = __ballot(seen);
+    if ((threadIdx.x & 63u) == 0 && bal) atomicAdd(&counters[CNT_DEL_GAPS_SEEN], (unsigned long long)__popcll(bal));
+}
+/* every k-mer of J_r = begin[0 : k - r] + end is in the graph: lane j <= k - r looks up k-mer j (Bloom filter, then the table); uniform in the wave */
+__device__ __forceinline__ bool del_joined_is_solid(const Index& ix, uint64_t begin, uint64_t end, int r, uint32_t lane, uint32_t& lines)
+{
+    const int k = ix.k;
+    bool solid = true;
+    if (lane <= (uint32_t)(k - r)) {
+        Kmer x;
+        x.r = del_joined_kmer(begin, end, r, (int)lane, k) ^ (0xAAAAAAAAAAAAAAAAULL & kmask(k));
+        x.f = revcomp(x.r, k);
+        solid = bloom_test(ix.bloom, x, k) && abundance(ix, x, lines) != 0;
+    }
+    return __ballot(!solid) == 0ull;
+}
+/* The observer on one candidate gap, one wave each (four to a workgroup): both k-mers are anchors, hence in the sequence and valid.
+ * res[c] = 0: no deletion; else DEL_CALLED | DEL_FALLBACK | r << 8 with the final r.  CNT_DEL_FALLBACK += 1 when J_0 held after J_r failed,
+ * CNT_DEL_CLEAN / CNT_DEL_FUZZY += 1 per call */
+__global__ void __launch_bounds__(FIND_WAVES * 64) k_del_judge(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off, const mtg_run* __restrict__ gaps,
+                                                               const uint32_t* __restrict__ cand, uint64_t ncand, int max_repeat, uint32_t* res, unsigned long long* counters)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t c = (uint64_t)blockIdx.x * FIND_WAVES + (threadIdx.x >> 6);
+    if (c >= ncand) return; /* (uniform in the wave; the kernel has no workgroup barrier) */
+    const mtg_run g = gaps[cand[c]];
+    const int k = ix.k;
+    const uint64_t* w = words + word_off[g.seq];
+    const uint64_t begin = del_packed_kmer(w, g.start - 1u, k), end = del_packed_kmer(w, g.start + g.length, k);
+    int r = del_fuzzy_site(begin, end, k, max_repeat);
+    uint32_t lines = 0;
+    bool called = del_joined_is_solid(ix, begin, end, r, lane, lines), fallback = false;
+    if (!called && r > 0) {
+        called = fallback = del_joined_is_solid(ix, begin, end, 0, lane, lines);
+        r = 0;
+    }
+    if (called && del_size_of(g.length, r, k) <= 0) called = false;
+    if (lane == 0) {
+        res[c] = called ? DEL_CALLED | (fallback ? DEL_FALLBACK : 0u) | ((uint32_t)r << DEL_REPEAT_SHIFT) : 0u;
+        if (fallback) atomicAdd(&counters[CNT_DEL_FALLBACK], 1ull);
+        if (called) atomicAdd(&counters[r ? CNT_DEL_FUZZY : CNT_DEL_CLEAN], 1ull);
+    }
+}
+/* the records of the calls: call j is candidate sel[j] */
+__global__ void __launch_bounds__(RUNS_BLOCK) k_del_emit(const mtg_run* __restrict__ gaps, const uint32_t* __restrict__ cand, const uint32_t* __restrict__ res,
+                                                        const uint32_t* __restrict__ sel, uint64_t n, int k, mtg_find_call* calls)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t c = sel[j];
+    const int r = (int)(res[c] >> DEL_REPEAT_SHIFT);
+    const mtg_run g = gaps[cand[c]];
+    mtg_find_call q;
+    q.seq = g.seq; q.pos = del_pos_of(g.start, r, k); q.kind = 4u; q.repeat = (uint32_t)r; q.left = g.start - 1u; q.right = g.start + g.length; q.ins = (uint32_t)del_size_of(g.length, r, k);
     calls[j] = q;
 }
 
@@ -1218,6 +1289,93 @@ int find_homo_run(const mtg_index* idx, const uint64_t* words, size_t nwords, co
     if (st) {
         st->n_positions = c[CNT_POSITIONS]; st->n_gaps = c[CNT_GAPS_SEEN]; st->n_candidates = n_cand;
         st->n_homo_clean = c[CNT_HOMO_CLEAN]; st->n_homo_fuzzy = c[CNT_HOMO_FUZZY]; st->n_small_clean = c[CNT_SMALL_CLEAN]; st->n_small_fuzzy = c[CNT_SMALL_FUZZY];
+        st->kernel_ms = (double)ms;
+    }
+    return MTG_OK;
+}
+
+/* `find` for homozygous deletions over packed sequences (mtg_index_find_del_sequences / _packed_device): the stage of find_homo_run with the
+ * deletion observer's mark, judge and emit.  device_ptrs as there */
+int find_del_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
+                 mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_del_stats* st)
+{
+    if (int rc = use_device_of(idx)) return rc;
+    if (!idx || !idx->dev.bloom.bits) { set_error("the index has no Bloom filter (MTG_BLOOM_BITS=0)"); return MTG_ERR_ARG; }
+    *n_calls = 0;
+    if (st) *st = mtg_find_del_stats{};
+    if (nseq == 0) return MTG_OK;
+    const int k = idx->dev.k;
+    if (max_repeat > k - 2) max_repeat = k - 2;
+    SeqInput in;
+    DevBuf d_v, d_p, d_cnt, d_before, d_c, d_gaps, d_mark, d_blk_cnt, d_blk_before, d_cand, d_res, d_sel, d_calls;
+    if (device_ptrs) in.take(words, word_off, len, nseq, bad);
+    else if (int rc = in.upload(words, nwords, word_off, len, nseq, bad)) return rc;
+    if (int rc = in.plane_words(&nwords)) return rc;
+    HIP_TRY(d_v.alloc(nwords * 8)); HIP_TRY(d_p.alloc(nwords * 8));
+    HIP_TRY(d_cnt.alloc(nseq * 4)); HIP_TRY(d_before.alloc(nseq * 8));
+    HIP_TRY(d_c.alloc(CNT_DEL_SLOTS * 8));
+    HIP_TRY(hipMemset(d_c.p, 0, CNT_DEL_SLOTS * 8));
+    unsigned long long* cnt = d_c.as<unsigned long long>();
+    EventSet events;
+    hipEvent_t ev[6];
+    for (hipEvent_t& e : ev) HIP_TRY(events.make(e));
+    const dim3 grid((unsigned)std::min<size_t>(nseq, 256 * 16));
+    unsigned long long c[CNT_DEL_SLOTS];
+    float ms = 0, part = 0;
+    /* 1. the planes, the gaps counted */
+    HIP_TRY(hipEventRecord(ev[0], 0));
+    hipLaunchKernelGGL(k_profile<false>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, in.words, in.word_off, in.len, nseq, in.bad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
+    hipLaunchKernelGGL(k_profile_count<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, d_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + CNT_GAPS);
+    HIP_TRY(hipEventRecord(ev[1], 0));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipEventElapsedTime(&part, ev[0], ev[1])); ms += part;
+    const uint64_t n_gaps_all = c[CNT_GAPS];
+    if (n_gaps_all > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 gaps"); return MTG_ERR_ARG; }
+    uint64_t n_cand = 0, total = 0;
+    if (n_gaps_all) {
+        /* 2. the gaps written, the candidates marked and listed in order */
+        HIP_TRY(d_gaps.alloc((size_t)n_gaps_all * sizeof(mtg_run)));
+        HIP_TRY(hipMemset(d_gaps.p, 0, (size_t)n_gaps_all * sizeof(mtg_run)));
+        HIP_TRY(d_mark.alloc((size_t)n_gaps_all * 4));
+        const unsigned gb = (unsigned)((n_gaps_all + RUNS_BLOCK - 1) / RUNS_BLOCK);
+        HIP_TRY(hipEventRecord(ev[2], 0));
+        hipLaunchKernelGGL(k_profile_write<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, d_before.as<uint64_t>(), d_gaps.as<mtg_run>(), n_gaps_all);
+        hipLaunchKernelGGL(k_profile_finish, dim3(std::min(gb, 256u * 16u)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, cnt + CNT_GAPS);
+        hipLaunchKernelGGL(k_del_mark, dim3(gb), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, k, max_repeat, d_mark.as<uint32_t>(), cnt);
+        if (int rc = mark_compact(d_mark.as<uint32_t>(), n_gaps_all, d_blk_cnt, d_blk_before, cnt + CNT_DEL_CANDIDATES, d_cand, ~0ull, &n_cand)) return rc;
+        HIP_TRY(hipEventRecord(ev[3], 0));
+    }
+    if (n_cand) {
+        /* 3. the observer, one wave per candidate; the calls listed in order and written */
+        HIP_TRY(d_res.alloc((size_t)n_cand * 4));
+        HIP_TRY(hipEventRecord(ev[4], 0));
+        hipLaunchKernelGGL(k_del_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, in.words, in.word_off, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(),
+                           n_cand, max_repeat, d_res.as<uint32_t>(), cnt);
+        if (int rc = mark_compact(d_res.as<uint32_t>(), n_cand, d_blk_cnt, d_blk_before, cnt + CNT_DEL_CALLS, d_sel, cap, &total)) return rc;
+        const uint64_t keep = std::min<uint64_t>(total, cap);
+        mtg_find_call* pc = calls;
+        if (keep) {
+            if (!device_ptrs) { HIP_TRY(d_calls.alloc((size_t)keep * sizeof(mtg_find_call))); pc = d_calls.as<mtg_find_call>(); }
+            hipLaunchKernelGGL(k_del_emit, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), d_res.as<uint32_t>(),
+                               d_sel.as<uint32_t>(), keep, k, pc);
+        }
+        HIP_TRY(hipEventRecord(ev[5], 0));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventSynchronize(ev[5]));
+        if (keep && !device_ptrs) HIP_TRY(hipMemcpy(calls, pc, (size_t)keep * sizeof(mtg_find_call), hipMemcpyDeviceToHost));
+        HIP_TRY(hipEventElapsedTime(&part, ev[4], ev[5])); ms += part;
+    }
+    if (n_gaps_all) {
+        HIP_TRY(hipEventSynchronize(ev[3]));
+        HIP_TRY(hipEventElapsedTime(&part, ev[2], ev[3])); ms += part;
+    }
+    HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
+    *n_calls = (size_t)total;
+    if (st) {
+        st->n_positions = c[CNT_POSITIONS]; st->n_gaps = c[CNT_DEL_GAPS_SEEN]; st->n_candidates = n_cand;
+        st->n_del_clean = c[CNT_DEL_CLEAN]; st->n_del_fuzzy = c[CNT_DEL_FUZZY]; st->n_fallback = c[CNT_DEL_FALLBACK]; st->n_calls = total;
         st->kernel_ms = (double)ms;
     }
     return MTG_OK;

@@ -136,6 +136,12 @@ __attribute__((weak)) int find_homo_run(const mtg_index*, const uint64_t*, size_
     set_error("this build has no device code for find");
     return MTG_ERR_NO_DEVICE;
 }
+__attribute__((weak)) int find_del_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, int, mtg_find_call*, size_t, size_t*, int,
+                                       mtg_find_del_stats*)
+{
+    set_error("this build has no device code for find");
+    return MTG_ERR_NO_DEVICE;
+}
 __attribute__((weak)) int find_het_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, const uint64_t*, int, int, mtg_find_call*, size_t,
                                        size_t*, int, mtg_find_het_stats*)
 {
@@ -1940,6 +1946,24 @@ int mtg_index_find_homo_packed_device(const mtg_index* idx, const uint64_t* d_wo
     if (!idx || !n_calls || (nseq && (!d_words || !d_word_off || !d_len)) || (cap && !d_calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
     if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
     return mtgi::find_homo_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, d_calls, cap, n_calls, 1, st);
+}
+
+int mtg_index_find_del_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_del_stats* st)
+{
+    if (!idx || !n_calls || (nseq && !seqs) || (cap && !calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
+    std::vector<uint64_t> off, pos_off, words, bad;
+    std::vector<uint32_t> len;
+    uint64_t npos = 0;
+    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, off, len, pos_off, npos, words, bad)) return MTG_ERR_ARG;
+    return mtgi::find_del_run(idx, words.data(), words.size(), off.data(), len.data(), nseq, bad.data(), max_repeat, calls, cap, n_calls, 0, st);
+}
+int mtg_index_find_del_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
+                                     mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_del_stats* st)
+{
+    if (!idx || !n_calls || (nseq && (!d_words || !d_word_off || !d_len)) || (cap && !d_calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
+    return mtgi::find_del_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, d_calls, cap, n_calls, 1, st);
 }
 
 int mtg_index_find_het_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, const uint8_t* const* repeated, int max_repeat, int branching_filter, mtg_find_call* calls,
