@@ -1446,6 +1446,19 @@ int profile_main(int argc, const char* const* argv)
     return 0;
 }
 
+/* The snprintf convention of the find entries: entry(calls, cap, &n) reports every call in n and writes at most cap of them.  When n
+ * exceeds the room, once more with room for all of them; it must not exceed it again */
+template <typename Entry> static int find_all_calls(std::vector<mtg_find_call>& calls, size_t& n, Entry entry)
+{
+    int rc = entry(calls.data(), calls.size(), &n);
+    if (!rc && n > calls.size()) {
+        calls.resize(n);
+        rc = entry(calls.data(), calls.size(), &n);
+    }
+    if (!rc && n > calls.size()) { rc = MTG_ERR_ARG; set_error("the number of calls changed between two calls"); }
+    return rc;
+}
+
 /* `MindTheGap find -homo-insertions | -hete-only | -insert-only`: the insertion sites and the insertions of 1-2 nt of a reference genome against
  * the graph, homozygous (mtg_index_find_homo_sequences), heterozygous (mtg_index_find_het_sequences) or both, in the reference's two files.
  * `-deletion-only | -homo-only -no-snp | -no-snp`: the reference's configurations of those names (src/Finder.cpp:320-398, :549-582), with the
@@ -1525,24 +1538,14 @@ int find_main(int argc, const char* const* argv)
     k = info.k;
     if (run_het && k < 12) { mtg_index_free(idx); fputs(small_k, stderr); return 1; }
     if (run_homo) {
-        rc = mtg_index_find_homo_sequences(idx, seqs.data(), seqs.size(), max_repeat, calls.data(), calls.size(), &n_calls, &st);
-        if (!rc && n_calls > calls.size()) { /* the snprintf convention: once more with room for all of them */
-            calls.resize(n_calls);
-            rc = mtg_index_find_homo_sequences(idx, seqs.data(), seqs.size(), max_repeat, calls.data(), calls.size(), &n_calls, &st);
-        }
-        if (!rc && n_calls > calls.size()) { rc = MTG_ERR_ARG; set_error("the number of calls changed between two calls"); }
+        rc = find_all_calls(calls, n_calls, [&](mtg_find_call* c, size_t cap, size_t* n) { return mtg_index_find_homo_sequences(idx, seqs.data(), seqs.size(), max_repeat, c, cap, n, &st); });
         if (!rc && !homo_sites) {
             n_calls = (size_t)(std::remove_if(calls.begin(), calls.begin() + (ptrdiff_t)n_calls, [](const mtg_find_call& c) { return c.kind == 0; }) - calls.begin());
             st.n_homo_clean = st.n_homo_fuzzy = 0;
         }
     }
     if (run_del && !rc) {
-        rc = mtg_index_find_del_sequences(idx, seqs.data(), seqs.size(), max_repeat, del_calls.data(), del_calls.size(), &n_del, nullptr);
-        if (!rc && n_del > del_calls.size()) {
-            del_calls.resize(n_del);
-            rc = mtg_index_find_del_sequences(idx, seqs.data(), seqs.size(), max_repeat, del_calls.data(), del_calls.size(), &n_del, nullptr);
-        }
-        if (!rc && n_del > del_calls.size()) { rc = MTG_ERR_ARG; set_error("the number of calls changed between two calls"); }
+        rc = find_all_calls(del_calls, n_del, [&](mtg_find_call* c, size_t cap, size_t* n) { return mtg_index_find_del_sequences(idx, seqs.data(), seqs.size(), max_repeat, c, cap, n, nullptr); });
     }
     if (run_het && !rc) {
         /* the repeated (k-1)-mers of the genome (fillRefBloom, src/FindBreakpoints.hpp:956-1008, as an exact set): an index of the genome file at
@@ -1561,12 +1564,7 @@ int find_main(int argc, const char* const* argv)
         }
         if (ridx) mtg_index_free(ridx);
         const uint8_t* const* rp = flag_ptrs.empty() ? nullptr : flag_ptrs.data();
-        if (!rc) rc = mtg_index_find_het_sequences(idx, seqs.data(), seqs.size(), rp, max_repeat, branching_filter, het_calls.data(), het_calls.size(), &n_het, &hst);
-        if (!rc && n_het > het_calls.size()) {
-            het_calls.resize(n_het);
-            rc = mtg_index_find_het_sequences(idx, seqs.data(), seqs.size(), rp, max_repeat, branching_filter, het_calls.data(), het_calls.size(), &n_het, &hst);
-        }
-        if (!rc && n_het > het_calls.size()) { rc = MTG_ERR_ARG; set_error("the number of calls changed between two calls"); }
+        if (!rc) rc = find_all_calls(het_calls, n_het, [&](mtg_find_call* c, size_t cap, size_t* n) { return mtg_index_find_het_sequences(idx, seqs.data(), seqs.size(), rp, max_repeat, branching_filter, c, cap, n, &hst); });
     }
     const double seconds = difftime(time(0), t_start);
     mtg_index_free(idx);

@@ -1,6 +1,6 @@
 /*
  * mtg_find_del.h -- the logic of `find` for homozygous deletions (FindDeletion::update, src/FindDeletion.hpp:58-188) on one gap of the scan
- * (mtg_find_gaps.h) and its two k-mers.  Shared by k_del_mark / k_del_judge / k_del_emit (mtg_gpu_misc.hip); the same source is compiled by
+ * (mtg_find_gaps.h) and its two k-mers.  Shared by DelObserver (k_gap_mark / k_gap_emit) and k_del_judge (mtg_gpu_misc.hip); the same source is compiled by
  * g++ into tests/emu/find_del.cpp, which checks it against literal string loops.
  *
  * The observer is a pure function of the gap: kmer_begin (the anchor right before the gap, at left = start - 1), kmer_end (the first anchor

@@ -316,14 +316,16 @@ __global__ void __launch_bounds__(SCAN_TILE) k_scan(Index ix, const uint64_t* __
     if (tid < SCAN_COUNTERS && s_tot[tid]) atomicAdd(&counters[tid], s_tot[tid]);
 }
 
-/* The counter block of profile_run / find_homo_run / find_het_run: 64-bit slots zeroed by the run, named here for its kernels and for the
+/* The counter block of profile_run and of the find runs (FindStage): 64-bit slots zeroed by the run, named here for its kernels and for the
  * host's read-back alike.  Every block begins with k_profile's three; a total and a longest run are neighbours (k_profile_seq_scan writes
- * tot[0], k_profile_finish tot[1]) */
+ * tot[0], k_profile_finish tot[1]).  The gap observers (homozygous insertions, deletions) share slots 4-8 and name their own from 10 up;
+ * the heterozygous run names its slots where they differ */
 enum { CNT_POSITIONS, CNT_VALID, CNT_PRESENT, CNT_PROFILE };
 enum { CNT_RUNS = 4, CNT_RUNS_LONGEST, CNT_PROFILE_SLOTS = 8 };
-enum { CNT_GAPS = 4, CNT_GAPS_LONGEST, CNT_HOMO_CANDIDATES, CNT_HOMO_CALLS, CNT_GAPS_SEEN, CNT_HOMO_CLEAN = 10, CNT_HOMO_FUZZY, CNT_SMALL_CLEAN, CNT_SMALL_FUZZY, CNT_HOMO_SLOTS = 16 };
-enum { CNT_DEL_CANDIDATES = 6, CNT_DEL_CALLS, CNT_DEL_GAPS_SEEN, CNT_DEL_CLEAN = 10, CNT_DEL_FUZZY, CNT_DEL_FALLBACK, CNT_DEL_SLOTS = 16 }; /* (CNT_GAPS, CNT_GAPS_LONGEST as above) */
-enum { CNT_HET_LISTED = 4, CNT_HET_CALLS = 6, CNT_HET_CANDIDATES = 8, CNT_HET_RAW_SITES, CNT_HET_FILTERED, CNT_HET_SUPPRESSED, CNT_HET_CLEAN, CNT_HET_FUZZY, CNT_HET_SMALL, CNT_HET_SLOTS = 16 };
+enum { CNT_GAPS = 4, CNT_GAPS_LONGEST, CNT_GAP_CANDIDATES, CNT_GAP_CALLS, CNT_GAPS_SEEN, CNT_FIND_SLOTS = 16 }; /* (CNT_GAPS: gaps of any kind) */
+enum { CNT_HOMO_CLEAN = 10, CNT_HOMO_FUZZY, CNT_SMALL_CLEAN, CNT_SMALL_FUZZY };
+enum { CNT_DEL_CLEAN = 10, CNT_DEL_FUZZY, CNT_DEL_FALLBACK };
+enum { CNT_HET_LISTED = 4, CNT_HET_CALLS = 6, CNT_HET_CANDIDATES = 8, CNT_HET_RAW_SITES, CNT_HET_FILTERED, CNT_HET_SUPPRESSED, CNT_HET_CLEAN, CNT_HET_FUZZY, CNT_HET_SMALL };
 
 /* profile along packed sequences: the tile of k_scan (scan_tile_stage: the tile's m-mers hashed once in LDS, Bloom blocks staged by coalesced
  * reads; then pre-filter, exact confirmation), and for the confirmed positions the abundance and the neighbour masks of k_query, packed into one
@@ -492,22 +494,34 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_profile_finish(mtg_run* runs, ui
     if (longest) atomicMax(&tot[1], (unsigned long long)longest);
 }
 
-/* ---- `find` for homozygous insertions (include/mtg_fill.h: mtg_index_find_homo_sequences).  The gaps of the scan come from
- * k_profile_count<true> / k_profile_write<true> as mtg_run records (flags: mtg_find_gaps.h).
- * k_find_mark: one thread per gap, the length test alone -- mark[i] = the gap is a candidate; CNT_GAPS_SEEN += gaps the observers see.
+/* ---- `find` over the gaps of the scan (include/mtg_fill.h: mtg_index_find_homo_sequences, mtg_index_find_del_sequences).  The gaps come from
+ * k_profile_count<true> / k_profile_write<true> as mtg_run records (flags: mtg_find_gaps.h).  An Observer (HomoObserver, DelObserver below) is
+ * one kind of call on a gap: its candidate test, its judge kernel, the record of a call and its statistics.
+ * k_gap_mark: one thread per gap, the observer's candidate test alone -- mark[i] = the gap is a candidate; CNT_GAPS_SEEN += gaps the observers see.
  * k_mark_count / k_profile_seq_scan / k_mark_index: the indices of the non-zero marks in ascending order (counts per workgroup, their
- * exclusive prefix sums, then every workgroup numbers its own); used for the candidates and, after k_find_assemble, for the calls. */
-__global__ void __launch_bounds__(RUNS_BLOCK) k_find_mark(const mtg_run* __restrict__ gaps, uint64_t n, int k, int max_repeat, uint32_t* mark, unsigned long long* counters)
+ * exclusive prefix sums, then every workgroup numbers its own); used for the candidates and, after the judge kernel, for the calls.
+ * k_gap_emit: the records of the calls: call j is candidate sel[j] */
+template <typename Observer>
+__global__ void __launch_bounds__(RUNS_BLOCK) k_gap_mark(const mtg_run* __restrict__ gaps, uint64_t n, int k, int max_repeat, uint32_t* mark, unsigned long long* counters)
 {
     const uint64_t i = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
     bool seen = false;
     if (i < n) {
         const mtg_run g = gaps[i];
         seen = (g.flags & 2u) != 0;
-        mark[i] = gap_is_candidate(g.length, g.flags, k, max_repeat) ? 1u : 0u;
+        mark[i] = Observer::is_candidate(g, k, max_repeat) ? 1u : 0u;
     }
     const unsigned long long bal = __ballot(seen);
     if ((threadIdx.x & 63u) == 0 && bal) atomicAdd(&counters[CNT_GAPS_SEEN], (unsigned long long)__popcll(bal));
+}
+template <typename Observer>
+__global__ void __launch_bounds__(RUNS_BLOCK) k_gap_emit(const mtg_run* __restrict__ gaps, const uint32_t* __restrict__ cand, const uint32_t* __restrict__ res,
+                                                        const uint32_t* __restrict__ sel, uint64_t n, int k, mtg_find_call* calls)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t c = sel[j];
+    calls[j] = Observer::call_of(gaps[cand[c]], res[c], k);
 }
 __global__ void __launch_bounds__(RUNS_BLOCK) k_mark_count(const uint32_t* __restrict__ mark, uint64_t n, uint32_t* blk_cnt)
 {
@@ -605,35 +619,31 @@ __global__ void __launch_bounds__(FIND_WAVES * 64) k_find_assemble(Index ix, con
         if (out) atomicAdd(&counters[((out >> 1) & 1u) ? (r ? CNT_SMALL_FUZZY : CNT_SMALL_CLEAN) : (r ? CNT_HOMO_FUZZY : CNT_HOMO_CLEAN)], 1ull);
     }
 }
-/* the records of the calls: call j is candidate sel[j] */
-__global__ void __launch_bounds__(RUNS_BLOCK) k_find_emit(const mtg_run* __restrict__ gaps, const uint32_t* __restrict__ cand, const uint32_t* __restrict__ res,
-                                                         const uint32_t* __restrict__ sel, uint64_t n, int k, mtg_find_call* calls)
-{
-    const uint64_t j = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t c = sel[j], o = res[c];
-    const mtg_run g = gaps[cand[c]];
-    const uint32_t e = g.start + g.length, r = (uint32_t)(k - 1) - g.length, kind = (o >> 1) & 1u;
-    mtg_find_call q;
-    q.seq = g.seq; q.pos = kind ? e - 1u : e - 1u + r; q.kind = kind; q.repeat = r; q.left = g.start - 1u; q.right = e + r; q.ins = o >> 8;
-    calls[j] = q;
-}
+/* the gap observer of the homozygous insertions: gap_is_candidate (mtg_find_gaps.h), k_find_assemble, kinds 0 (site) and 1 (1-2 nt) */
+struct HomoObserver {
+    using Stats = mtg_find_stats;
+    static MTG_DEV bool is_candidate(const mtg_run& g, int k, int max_repeat) { return gap_is_candidate(g.length, g.flags, k, max_repeat); }
+    static void judge(const Index& ix, const uint64_t* words, const uint64_t* word_off, const uint32_t* len, const uint64_t* bad, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand,
+                      int, uint32_t* res, unsigned long long* cnt)
+    {
+        hipLaunchKernelGGL(k_find_assemble, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, ix, words, word_off, len, bad, gaps, cand, n_cand, res, cnt);
+    }
+    static MTG_DEV mtg_find_call call_of(const mtg_run& g, uint32_t o, int k)
+    {
+        const uint32_t e = g.start + g.length, r = (uint32_t)(k - 1) - g.length, kind = (o >> 1) & 1u;
+        mtg_find_call q;
+        q.seq = g.seq; q.pos = kind ? e - 1u : e - 1u + r; q.kind = kind; q.repeat = r; q.left = g.start - 1u; q.right = e + r; q.ins = o >> 8;
+        return q;
+    }
+    static void fill(Stats& st, const unsigned long long* c, uint64_t n_cand, uint64_t)
+    {
+        st.n_positions = c[CNT_POSITIONS]; st.n_gaps = c[CNT_GAPS_SEEN]; st.n_candidates = n_cand;
+        st.n_homo_clean = c[CNT_HOMO_CLEAN]; st.n_homo_fuzzy = c[CNT_HOMO_FUZZY]; st.n_small_clean = c[CNT_SMALL_CLEAN]; st.n_small_fuzzy = c[CNT_SMALL_FUZZY];
+    }
+};
 
 /* ---- `find` for homozygous deletions (include/mtg_fill.h: mtg_index_find_del_sequences; the rule: mtg_find_del.h).  The gaps are those of the
- * insertion observers (k_profile_count<true> / k_profile_write<true>), the candidates and the calls are listed by k_mark_*.
- * k_del_mark: one thread per gap, the candidate test alone; CNT_DEL_GAPS_SEEN += gaps the observers see. */
-__global__ void __launch_bounds__(RUNS_BLOCK) k_del_mark(const mtg_run* __restrict__ gaps, uint64_t n, int k, int max_repeat, uint32_t* mark, unsigned long long* counters)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
-    bool seen = false;
-    if (i < n) {
-        const mtg_run g = gaps[i];
-        seen = (g.flags & 2u) != 0;
-        mark[i] = gap_is_del_candidate(g.length, g.flags, k, max_repeat) ? 1u : 0u;
-    }
-    const unsigned long long bal = __ballot(seen);
-    if ((threadIdx.x & 63u) == 0 && bal) atomicAdd(&counters[CNT_DEL_GAPS_SEEN], (unsigned long long)__popcll(bal));
-}
+ * insertion observers, marked, listed and emitted by the same kernels (k_gap_mark, k_mark_*, k_gap_emit) for DelObserver. */
 /* every k-mer of J_r = begin[0 : k - r] + end is in the graph: lane j <= k - r looks up k-mer j (Bloom filter, then the table); uniform in the wave */
 __device__ __forceinline__ bool del_joined_is_solid(const Index& ix, uint64_t begin, uint64_t end, int r, uint32_t lane, uint32_t& lines)
 {
@@ -674,19 +684,28 @@ __global__ void __launch_bounds__(FIND_WAVES * 64) k_del_judge(Index ix, const u
         if (called) atomicAdd(&counters[r ? CNT_DEL_FUZZY : CNT_DEL_CLEAN], 1ull);
     }
 }
-/* the records of the calls: call j is candidate sel[j] */
-__global__ void __launch_bounds__(RUNS_BLOCK) k_del_emit(const mtg_run* __restrict__ gaps, const uint32_t* __restrict__ cand, const uint32_t* __restrict__ res,
-                                                        const uint32_t* __restrict__ sel, uint64_t n, int k, mtg_find_call* calls)
-{
-    const uint64_t j = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t c = sel[j];
-    const int r = (int)(res[c] >> DEL_REPEAT_SHIFT);
-    const mtg_run g = gaps[cand[c]];
-    mtg_find_call q;
-    q.seq = g.seq; q.pos = del_pos_of(g.start, r, k); q.kind = 4u; q.repeat = (uint32_t)r; q.left = g.start - 1u; q.right = g.start + g.length; q.ins = (uint32_t)del_size_of(g.length, r, k);
-    calls[j] = q;
-}
+/* the gap observer of the homozygous deletions: gap_is_del_candidate (mtg_find_del.h), k_del_judge, kind 4 */
+struct DelObserver {
+    using Stats = mtg_find_del_stats;
+    static MTG_DEV bool is_candidate(const mtg_run& g, int k, int max_repeat) { return gap_is_del_candidate(g.length, g.flags, k, max_repeat); }
+    static void judge(const Index& ix, const uint64_t* words, const uint64_t* word_off, const uint32_t*, const uint64_t*, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand,
+                      int max_repeat, uint32_t* res, unsigned long long* cnt)
+    {
+        hipLaunchKernelGGL(k_del_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, ix, words, word_off, gaps, cand, n_cand, max_repeat, res, cnt);
+    }
+    static MTG_DEV mtg_find_call call_of(const mtg_run& g, uint32_t o, int k)
+    {
+        const int r = (int)(o >> DEL_REPEAT_SHIFT);
+        mtg_find_call q;
+        q.seq = g.seq; q.pos = del_pos_of(g.start, r, k); q.kind = 4u; q.repeat = (uint32_t)r; q.left = g.start - 1u; q.right = g.start + g.length; q.ins = (uint32_t)del_size_of(g.length, r, k);
+        return q;
+    }
+    static void fill(Stats& st, const unsigned long long* c, uint64_t n_cand, uint64_t total)
+    {
+        st.n_positions = c[CNT_POSITIONS]; st.n_gaps = c[CNT_GAPS_SEEN]; st.n_candidates = n_cand;
+        st.n_del_clean = c[CNT_DEL_CLEAN]; st.n_del_fuzzy = c[CNT_DEL_FUZZY]; st.n_fallback = c[CNT_DEL_FALLBACK]; st.n_calls = total;
+    }
+};
 
 /* ---- `find` for heterozygous insertions (include/mtg_fill.h: mtg_index_find_het_sequences; the rule and the word-level logic: mtg_find_het.h).
  * k_profile<true> writes the planes.  k_het_count / k_profile_seq_scan / k_het_list: the candidate positions in scan order by the two counted
@@ -1089,6 +1108,115 @@ private:
         return MTG_OK;
     }
 };
+
+/* What the find runs (find_gap_run, find_het_run) set up and end with alike: the input, the planes (HET: five of them), the per-sequence counts,
+ * the counter block and its host image c, the events of the two spans every run has, the scratch of compact() and the kernel time.  All device
+ * work goes to the null stream; DESIGN.md lists it per operation */
+struct FindStage {
+    SeqInput in;
+    DevBuf d_v, d_p, d_in2, d_out2, d_br, d_cnt, d_before, d_c, d_blk_cnt, d_blk_before, d_sel, d_calls;
+    unsigned long long c[CNT_FIND_SLOTS] = {};
+    EventSet events;
+    hipEvent_t e_planes[2], e_tail[2];
+    const mtg_index* idx = nullptr;
+    size_t nseq = 0;
+    int k = 0, max_repeat = 0, device_ptrs = 0;
+    float ms = 0;
+
+    unsigned long long* cnt() { return d_c.as<unsigned long long>(); }
+    dim3 grid() const { return dim3((unsigned)std::min<size_t>(nseq, 256 * 16)); }
+    int add_span(hipEvent_t from, hipEvent_t to) { float part = 0; HIP_TRY(hipEventElapsedTime(&part, from, to)); ms += part; return MTG_OK; }
+    int read_counters() { HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost)); return MTG_OK; }
+
+    /* The checks, *n_calls and the statistics zeroed; then, unless there is no sequence (the caller returns), the input taken or uploaded, the
+     * planes and counts allocated, the counters zeroed.  device_ptrs = 0: words / word_off / len / bad / rep are host arrays (nwords words
+     * each), 1: device memory (nwords unused) */
+    template <typename Stats>
+    int begin(const mtg_index* index, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t n, const uint64_t* bad, const uint64_t* rep, bool het,
+              int max_rep, size_t* n_calls, Stats* st, int dev_ptrs)
+    {
+        if (int rc = use_device_of(index)) return rc;
+        if (!index || !index->dev.bloom.bits) { set_error("the index has no Bloom filter (MTG_BLOOM_BITS=0)"); return MTG_ERR_ARG; }
+        *n_calls = 0;
+        if (st) *st = Stats{};
+        if (n == 0) return MTG_OK;
+        idx = index; nseq = n; k = idx->dev.k; device_ptrs = dev_ptrs;
+        max_repeat = max_rep > k - 2 ? k - 2 : max_rep;
+        if (device_ptrs) in.take(words, word_off, len, nseq, bad, rep);
+        else if (int rc = in.upload(words, nwords, word_off, len, nseq, bad, rep)) return rc;
+        if (int rc = in.plane_words(&nwords)) return rc;
+        HIP_TRY(d_v.alloc(nwords * 8)); HIP_TRY(d_p.alloc(nwords * 8));
+        if (het) { HIP_TRY(d_in2.alloc(nwords * 8)); HIP_TRY(d_out2.alloc(nwords * 8)); HIP_TRY(d_br.alloc(nwords * 8)); }
+        HIP_TRY(d_cnt.alloc(nseq * 4)); HIP_TRY(d_before.alloc(nseq * 8));
+        HIP_TRY(d_c.alloc(sizeof c));
+        HIP_TRY(hipMemset(d_c.p, 0, sizeof c));
+        for (hipEvent_t* e : {&e_planes[0], &e_planes[1], &e_tail[0], &e_tail[1]}) HIP_TRY(events.make(*e));
+        return MTG_OK;
+    }
+    /* k_profile<HET>, the caller's count kernel (per sequence, into d_cnt) and their prefix sums, the total in slot `slot`: one span.  The
+     * counters come back (the one wait); *total is refused from 2^32 on */
+    template <bool HET, typename Count> int planes(Count launch_count, int slot, const char* what, uint64_t* total)
+    {
+        HIP_TRY(hipEventRecord(e_planes[0], 0));
+        hipLaunchKernelGGL(k_profile<HET>, grid(), dim3(SCAN_TILE), 0, 0, idx->dev, in.words, in.word_off, in.len, nseq, in.bad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt(),
+                           d_in2.as<uint64_t>(), d_out2.as<uint64_t>(), d_br.as<uint64_t>()); /* (null unless HET) */
+        launch_count();
+        hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt() + slot);
+        HIP_TRY(hipEventRecord(e_planes[1], 0));
+        HIP_TRY(hipGetLastError());
+        if (int rc = read_counters()) return rc;
+        if (int rc = add_span(e_planes[0], e_planes[1])) return rc;
+        *total = c[slot];
+        if (*total > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 %s", what); return MTG_ERR_ARG; }
+        return MTG_OK;
+    }
+    /* the n gaps written in (seq, start) order, the longest into CNT_GAPS_LONGEST; `from` is recorded ahead of the two kernels, the span is the caller's to end */
+    int gaps(uint64_t n, DevBuf& d_gaps, hipEvent_t from)
+    {
+        HIP_TRY(d_gaps.alloc((size_t)n * sizeof(mtg_run)));
+        HIP_TRY(hipMemset(d_gaps.p, 0, (size_t)n * sizeof(mtg_run)));
+        HIP_TRY(hipEventRecord(from, 0));
+        hipLaunchKernelGGL(k_profile_write<true>, grid(), dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, d_before.as<uint64_t>(), d_gaps.as<mtg_run>(), n);
+        hipLaunchKernelGGL(k_profile_finish, dim3((unsigned)std::min<uint64_t>((n + RUNS_BLOCK - 1) / RUNS_BLOCK, 256 * 16)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n, cnt() + CNT_GAPS);
+        return MTG_OK;
+    }
+    /* the indices of the non-zero marks in ascending order (k_mark_count, k_profile_seq_scan, k_mark_index): *total = how many, written to
+     * slot `slot` as well; index receives min(*total, cap) of them (allocated here).  Synchronises once, to read the total */
+    int compact(const uint32_t* mark, uint64_t n, int slot, DevBuf& index, uint64_t cap, uint64_t* total)
+    {
+        const unsigned nb = (unsigned)((n + RUNS_BLOCK - 1) / RUNS_BLOCK);
+        HIP_TRY(d_blk_cnt.alloc((size_t)nb * 4)); HIP_TRY(d_blk_before.alloc((size_t)nb * 8));
+        hipLaunchKernelGGL(k_mark_count, dim3(nb), dim3(RUNS_BLOCK), 0, 0, mark, n, d_blk_cnt.as<uint32_t>());
+        hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_blk_cnt.as<uint32_t>(), (size_t)nb, d_blk_before.as<uint64_t>(), cnt() + slot);
+        HIP_TRY(hipGetLastError());
+        unsigned long long t = 0;
+        HIP_TRY(hipMemcpy(&t, cnt() + slot, 8, hipMemcpyDeviceToHost));
+        *total = t;
+        const uint64_t keep = std::min<uint64_t>(t, cap);
+        HIP_TRY(index.alloc((size_t)keep * 4));
+        if (keep) hipLaunchKernelGGL(k_mark_index, dim3(nb), dim3(RUNS_BLOCK), 0, 0, mark, n, d_blk_before.as<uint64_t>(), index.as<uint32_t>(), keep);
+        HIP_TRY(hipGetLastError());
+        return MTG_OK;
+    }
+    /* What every run ends with, the caller having recorded e_tail[0] ahead of its judging: the non-zero entries of mark[0 : n] are the calls,
+     * counted into slot `slot`; emit(sel, keep, out) launches the kernel that writes the first keep = min(*total, cap) records, call j from
+     * entry sel[j], into device memory; they reach `calls` (the caller's device array, or host memory by one copy).  Ends the span and waits for it */
+    template <typename Emit> int calls_tail(const uint32_t* mark, uint64_t n, int slot, mtg_find_call* calls, size_t cap, uint64_t* total, Emit emit)
+    {
+        if (int rc = compact(mark, n, slot, d_sel, cap, total)) return rc;
+        const uint64_t keep = std::min<uint64_t>(*total, cap);
+        mtg_find_call* pc = calls;
+        if (keep) {
+            if (!device_ptrs) { HIP_TRY(d_calls.alloc((size_t)keep * sizeof(mtg_find_call))); pc = d_calls.as<mtg_find_call>(); }
+            emit(d_sel.as<uint32_t>(), keep, pc);
+        }
+        HIP_TRY(hipEventRecord(e_tail[1], 0));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventSynchronize(e_tail[1]));
+        if (keep && !device_ptrs) HIP_TRY(hipMemcpy(calls, pc, (size_t)keep * sizeof(mtg_find_call), hipMemcpyDeviceToHost));
+        return add_span(e_tail[0], e_tail[1]);
+    }
+};
 } // namespace
 
 int scan_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, int mode, uint64_t* out_bits,
@@ -1188,197 +1316,61 @@ int profile_run(const mtg_index* idx, const uint64_t* words, size_t nwords, cons
     return MTG_OK;
 }
 
-/* the indices of the non-zero marks in ascending order (k_mark_count, k_profile_seq_scan, k_mark_index): *total = how many; index receives
- * min(*total, cap) of them (allocated here).  Synchronises once, to read the total */
-static int mark_compact(const uint32_t* mark, uint64_t n, DevBuf& d_blk_cnt, DevBuf& d_blk_before, unsigned long long* d_tot, DevBuf& index, uint64_t cap, uint64_t* total)
+/* `find` by a gap observer over packed sequences.  device_ptrs = 0: words / word_off / len / bad are host arrays and calls host memory; 1: all
+ * of them device memory (nwords unused, bad null) */
+template <typename Observer>
+static int find_gap_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
+                        mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, typename Observer::Stats* st)
 {
-    const unsigned nb = (unsigned)((n + RUNS_BLOCK - 1) / RUNS_BLOCK);
-    HIP_TRY(d_blk_cnt.alloc((size_t)nb * 4)); HIP_TRY(d_blk_before.alloc((size_t)nb * 8));
-    hipLaunchKernelGGL(k_mark_count, dim3(nb), dim3(RUNS_BLOCK), 0, 0, mark, n, d_blk_cnt.as<uint32_t>());
-    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_blk_cnt.as<uint32_t>(), (size_t)nb, d_blk_before.as<uint64_t>(), d_tot);
-    HIP_TRY(hipGetLastError());
-    unsigned long long t = 0;
-    HIP_TRY(hipMemcpy(&t, d_tot, 8, hipMemcpyDeviceToHost));
-    *total = t;
-    const uint64_t keep = std::min<uint64_t>(t, cap);
-    HIP_TRY(index.alloc((size_t)keep * 4));
-    if (keep) hipLaunchKernelGGL(k_mark_index, dim3(nb), dim3(RUNS_BLOCK), 0, 0, mark, n, d_blk_before.as<uint64_t>(), index.as<uint32_t>(), keep);
-    HIP_TRY(hipGetLastError());
-    return MTG_OK;
-}
-
-/* `find` for homozygous insertions over packed sequences (mtg_index_find_homo_sequences / _packed_device).  device_ptrs = 0: words / word_off /
- * len / bad are host arrays and calls host memory; 1: all of them device memory (nwords unused, bad null) */
-int find_homo_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
-                  mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_stats* st)
-{
-    if (int rc = use_device_of(idx)) return rc;
-    if (!idx || !idx->dev.bloom.bits) { set_error("the index has no Bloom filter (MTG_BLOOM_BITS=0)"); return MTG_ERR_ARG; }
-    *n_calls = 0;
-    if (st) *st = mtg_find_stats{};
-    if (nseq == 0) return MTG_OK;
-    const int k = idx->dev.k;
-    if (max_repeat > k - 2) max_repeat = k - 2;
-    SeqInput in;
-    DevBuf d_v, d_p, d_cnt, d_before, d_c, d_gaps, d_mark, d_blk_cnt, d_blk_before, d_cand, d_res, d_sel, d_calls;
-    if (device_ptrs) in.take(words, word_off, len, nseq, bad);
-    else if (int rc = in.upload(words, nwords, word_off, len, nseq, bad)) return rc;
-    if (int rc = in.plane_words(&nwords)) return rc;
-    HIP_TRY(d_v.alloc(nwords * 8)); HIP_TRY(d_p.alloc(nwords * 8));
-    HIP_TRY(d_cnt.alloc(nseq * 4)); HIP_TRY(d_before.alloc(nseq * 8));
-    HIP_TRY(d_c.alloc(CNT_HOMO_SLOTS * 8));
-    HIP_TRY(hipMemset(d_c.p, 0, CNT_HOMO_SLOTS * 8));
-    unsigned long long* cnt = d_c.as<unsigned long long>(); /* (CNT_GAPS: gaps of any kind) */
-    EventSet events;
-    hipEvent_t ev[8];
-    for (hipEvent_t& e : ev) HIP_TRY(events.make(e));
-    const dim3 grid((unsigned)std::min<size_t>(nseq, 256 * 16));
-    unsigned long long c[CNT_HOMO_SLOTS];
-    float ms = 0, part = 0;
+    FindStage S;
+    if (int rc = S.begin(idx, words, nwords, word_off, len, nseq, bad, nullptr, false, max_repeat, n_calls, st, device_ptrs); rc || nseq == 0) return rc;
+    const int k = S.k;
+    const SeqInput& in = S.in;
+    DevBuf d_gaps, d_mark, d_cand, d_res;
+    hipEvent_t e_gaps[2];
+    HIP_TRY(S.events.make(e_gaps[0])); HIP_TRY(S.events.make(e_gaps[1]));
+    uint64_t n_gaps_all = 0, n_cand = 0, total = 0;
     /* 1. the planes, the gaps counted */
-    HIP_TRY(hipEventRecord(ev[0], 0));
-    hipLaunchKernelGGL(k_profile<false>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, in.words, in.word_off, in.len, nseq, in.bad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
-    hipLaunchKernelGGL(k_profile_count<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, d_cnt.as<uint32_t>());
-    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + CNT_GAPS);
-    HIP_TRY(hipEventRecord(ev[1], 0));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
-    HIP_TRY(hipEventElapsedTime(&part, ev[0], ev[1])); ms += part;
-    const uint64_t n_gaps_all = c[CNT_GAPS];
-    if (n_gaps_all > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 gaps"); return MTG_ERR_ARG; }
-    uint64_t n_cand = 0, total = 0;
+    if (int rc = S.planes<false>([&] { hipLaunchKernelGGL(k_profile_count<true>, S.grid(), dim3(RUNS_BLOCK), 0, 0, S.d_v.as<uint64_t>(), S.d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, S.d_cnt.as<uint32_t>()); },
+                                 CNT_GAPS, "gaps", &n_gaps_all)) return rc;
     if (n_gaps_all) {
         /* 2. the gaps written, the candidates marked and listed in order */
-        HIP_TRY(d_gaps.alloc((size_t)n_gaps_all * sizeof(mtg_run)));
-        HIP_TRY(hipMemset(d_gaps.p, 0, (size_t)n_gaps_all * sizeof(mtg_run)));
         HIP_TRY(d_mark.alloc((size_t)n_gaps_all * 4));
-        const unsigned gb = (unsigned)((n_gaps_all + RUNS_BLOCK - 1) / RUNS_BLOCK);
-        HIP_TRY(hipEventRecord(ev[2], 0));
-        hipLaunchKernelGGL(k_profile_write<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, d_before.as<uint64_t>(), d_gaps.as<mtg_run>(), n_gaps_all);
-        hipLaunchKernelGGL(k_profile_finish, dim3(std::min(gb, 256u * 16u)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, cnt + CNT_GAPS);
-        hipLaunchKernelGGL(k_find_mark, dim3(gb), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, k, max_repeat, d_mark.as<uint32_t>(), cnt);
-        if (int rc = mark_compact(d_mark.as<uint32_t>(), n_gaps_all, d_blk_cnt, d_blk_before, cnt + CNT_HOMO_CANDIDATES, d_cand, ~0ull, &n_cand)) return rc;
-        HIP_TRY(hipEventRecord(ev[3], 0));
-    }
-    if (n_cand) {
-        /* 3. the observers, one wave per candidate; the calls listed in order and written */
-        HIP_TRY(d_res.alloc((size_t)n_cand * 4));
-        HIP_TRY(hipEventRecord(ev[4], 0));
-        hipLaunchKernelGGL(k_find_assemble, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, in.words, in.word_off, in.len, in.bad, d_gaps.as<mtg_run>(),
-                           d_cand.as<uint32_t>(), n_cand, d_res.as<uint32_t>(), cnt);
-        if (int rc = mark_compact(d_res.as<uint32_t>(), n_cand, d_blk_cnt, d_blk_before, cnt + CNT_HOMO_CALLS, d_sel, cap, &total)) return rc;
-        const uint64_t keep = std::min<uint64_t>(total, cap);
-        mtg_find_call* pc = calls;
-        if (keep) {
-            if (!device_ptrs) { HIP_TRY(d_calls.alloc((size_t)keep * sizeof(mtg_find_call))); pc = d_calls.as<mtg_find_call>(); }
-            hipLaunchKernelGGL(k_find_emit, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(),
-                               d_res.as<uint32_t>(), d_sel.as<uint32_t>(), keep, k, pc);
-        }
-        HIP_TRY(hipEventRecord(ev[5], 0));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventSynchronize(ev[5]));
-        if (keep && !device_ptrs) HIP_TRY(hipMemcpy(calls, pc, (size_t)keep * sizeof(mtg_find_call), hipMemcpyDeviceToHost));
-        HIP_TRY(hipEventElapsedTime(&part, ev[4], ev[5])); ms += part;
-    }
-    if (n_gaps_all) {
-        HIP_TRY(hipEventSynchronize(ev[3]));
-        HIP_TRY(hipEventElapsedTime(&part, ev[2], ev[3])); ms += part;
-    }
-    HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
-    *n_calls = (size_t)total;
-    if (st) {
-        st->n_positions = c[CNT_POSITIONS]; st->n_gaps = c[CNT_GAPS_SEEN]; st->n_candidates = n_cand;
-        st->n_homo_clean = c[CNT_HOMO_CLEAN]; st->n_homo_fuzzy = c[CNT_HOMO_FUZZY]; st->n_small_clean = c[CNT_SMALL_CLEAN]; st->n_small_fuzzy = c[CNT_SMALL_FUZZY];
-        st->kernel_ms = (double)ms;
-    }
-    return MTG_OK;
-}
-
-/* `find` for homozygous deletions over packed sequences (mtg_index_find_del_sequences / _packed_device): the stage of find_homo_run with the
- * deletion observer's mark, judge and emit.  device_ptrs as there */
-int find_del_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
-                 mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_del_stats* st)
-{
-    if (int rc = use_device_of(idx)) return rc;
-    if (!idx || !idx->dev.bloom.bits) { set_error("the index has no Bloom filter (MTG_BLOOM_BITS=0)"); return MTG_ERR_ARG; }
-    *n_calls = 0;
-    if (st) *st = mtg_find_del_stats{};
-    if (nseq == 0) return MTG_OK;
-    const int k = idx->dev.k;
-    if (max_repeat > k - 2) max_repeat = k - 2;
-    SeqInput in;
-    DevBuf d_v, d_p, d_cnt, d_before, d_c, d_gaps, d_mark, d_blk_cnt, d_blk_before, d_cand, d_res, d_sel, d_calls;
-    if (device_ptrs) in.take(words, word_off, len, nseq, bad);
-    else if (int rc = in.upload(words, nwords, word_off, len, nseq, bad)) return rc;
-    if (int rc = in.plane_words(&nwords)) return rc;
-    HIP_TRY(d_v.alloc(nwords * 8)); HIP_TRY(d_p.alloc(nwords * 8));
-    HIP_TRY(d_cnt.alloc(nseq * 4)); HIP_TRY(d_before.alloc(nseq * 8));
-    HIP_TRY(d_c.alloc(CNT_DEL_SLOTS * 8));
-    HIP_TRY(hipMemset(d_c.p, 0, CNT_DEL_SLOTS * 8));
-    unsigned long long* cnt = d_c.as<unsigned long long>();
-    EventSet events;
-    hipEvent_t ev[6];
-    for (hipEvent_t& e : ev) HIP_TRY(events.make(e));
-    const dim3 grid((unsigned)std::min<size_t>(nseq, 256 * 16));
-    unsigned long long c[CNT_DEL_SLOTS];
-    float ms = 0, part = 0;
-    /* 1. the planes, the gaps counted */
-    HIP_TRY(hipEventRecord(ev[0], 0));
-    hipLaunchKernelGGL(k_profile<false>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, in.words, in.word_off, in.len, nseq, in.bad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr);
-    hipLaunchKernelGGL(k_profile_count<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, d_cnt.as<uint32_t>());
-    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + CNT_GAPS);
-    HIP_TRY(hipEventRecord(ev[1], 0));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
-    HIP_TRY(hipEventElapsedTime(&part, ev[0], ev[1])); ms += part;
-    const uint64_t n_gaps_all = c[CNT_GAPS];
-    if (n_gaps_all > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 gaps"); return MTG_ERR_ARG; }
-    uint64_t n_cand = 0, total = 0;
-    if (n_gaps_all) {
-        /* 2. the gaps written, the candidates marked and listed in order */
-        HIP_TRY(d_gaps.alloc((size_t)n_gaps_all * sizeof(mtg_run)));
-        HIP_TRY(hipMemset(d_gaps.p, 0, (size_t)n_gaps_all * sizeof(mtg_run)));
-        HIP_TRY(d_mark.alloc((size_t)n_gaps_all * 4));
-        const unsigned gb = (unsigned)((n_gaps_all + RUNS_BLOCK - 1) / RUNS_BLOCK);
-        HIP_TRY(hipEventRecord(ev[2], 0));
-        hipLaunchKernelGGL(k_profile_write<true>, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, d_before.as<uint64_t>(), d_gaps.as<mtg_run>(), n_gaps_all);
-        hipLaunchKernelGGL(k_profile_finish, dim3(std::min(gb, 256u * 16u)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, cnt + CNT_GAPS);
-        hipLaunchKernelGGL(k_del_mark, dim3(gb), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, k, max_repeat, d_mark.as<uint32_t>(), cnt);
-        if (int rc = mark_compact(d_mark.as<uint32_t>(), n_gaps_all, d_blk_cnt, d_blk_before, cnt + CNT_DEL_CANDIDATES, d_cand, ~0ull, &n_cand)) return rc;
-        HIP_TRY(hipEventRecord(ev[3], 0));
+        if (int rc = S.gaps(n_gaps_all, d_gaps, e_gaps[0])) return rc;
+        hipLaunchKernelGGL(k_gap_mark<Observer>, dim3((unsigned)((n_gaps_all + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, k, S.max_repeat, d_mark.as<uint32_t>(), S.cnt());
+        if (int rc = S.compact(d_mark.as<uint32_t>(), n_gaps_all, CNT_GAP_CANDIDATES, d_cand, ~0ull, &n_cand)) return rc;
+        HIP_TRY(hipEventRecord(e_gaps[1], 0));
     }
     if (n_cand) {
         /* 3. the observer, one wave per candidate; the calls listed in order and written */
         HIP_TRY(d_res.alloc((size_t)n_cand * 4));
-        HIP_TRY(hipEventRecord(ev[4], 0));
-        hipLaunchKernelGGL(k_del_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, in.words, in.word_off, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(),
-                           n_cand, max_repeat, d_res.as<uint32_t>(), cnt);
-        if (int rc = mark_compact(d_res.as<uint32_t>(), n_cand, d_blk_cnt, d_blk_before, cnt + CNT_DEL_CALLS, d_sel, cap, &total)) return rc;
-        const uint64_t keep = std::min<uint64_t>(total, cap);
-        mtg_find_call* pc = calls;
-        if (keep) {
-            if (!device_ptrs) { HIP_TRY(d_calls.alloc((size_t)keep * sizeof(mtg_find_call))); pc = d_calls.as<mtg_find_call>(); }
-            hipLaunchKernelGGL(k_del_emit, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), d_res.as<uint32_t>(),
-                               d_sel.as<uint32_t>(), keep, k, pc);
-        }
-        HIP_TRY(hipEventRecord(ev[5], 0));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventSynchronize(ev[5]));
-        if (keep && !device_ptrs) HIP_TRY(hipMemcpy(calls, pc, (size_t)keep * sizeof(mtg_find_call), hipMemcpyDeviceToHost));
-        HIP_TRY(hipEventElapsedTime(&part, ev[4], ev[5])); ms += part;
+        HIP_TRY(hipEventRecord(S.e_tail[0], 0));
+        Observer::judge(idx->dev, in.words, in.word_off, in.len, in.bad, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), n_cand, S.max_repeat, d_res.as<uint32_t>(), S.cnt());
+        if (int rc = S.calls_tail(d_res.as<uint32_t>(), n_cand, CNT_GAP_CALLS, calls, cap, &total, [&](const uint32_t* sel, uint64_t keep, mtg_find_call* out) {
+                hipLaunchKernelGGL(k_gap_emit<Observer>, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), d_res.as<uint32_t>(), sel, keep, k, out);
+            })) return rc;
     }
     if (n_gaps_all) {
-        HIP_TRY(hipEventSynchronize(ev[3]));
-        HIP_TRY(hipEventElapsedTime(&part, ev[2], ev[3])); ms += part;
+        HIP_TRY(hipEventSynchronize(e_gaps[1]));
+        if (int rc = S.add_span(e_gaps[0], e_gaps[1])) return rc;
     }
-    HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
+    if (int rc = S.read_counters()) return rc;
     *n_calls = (size_t)total;
-    if (st) {
-        st->n_positions = c[CNT_POSITIONS]; st->n_gaps = c[CNT_DEL_GAPS_SEEN]; st->n_candidates = n_cand;
-        st->n_del_clean = c[CNT_DEL_CLEAN]; st->n_del_fuzzy = c[CNT_DEL_FUZZY]; st->n_fallback = c[CNT_DEL_FALLBACK]; st->n_calls = total;
-        st->kernel_ms = (double)ms;
-    }
+    if (st) { Observer::fill(*st, S.c, n_cand, total); st->kernel_ms = (double)S.ms; }
     return MTG_OK;
+}
+
+/* `find` for homozygous insertions (mtg_index_find_homo_sequences / _packed_device) and for homozygous deletions (mtg_index_find_del_sequences /
+ * _packed_device): the gap run with their observers */
+int find_homo_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
+                  mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_stats* st)
+{
+    return find_gap_run<HomoObserver>(idx, words, nwords, word_off, len, nseq, bad, max_repeat, calls, cap, n_calls, device_ptrs, st);
+}
+int find_del_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
+                 mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_del_stats* st)
+{
+    return find_gap_run<DelObserver>(idx, words, nwords, word_off, len, nseq, bad, max_repeat, calls, cap, n_calls, device_ptrs, st);
 }
 
 /* `find` for heterozygous insertions over packed sequences (mtg_index_find_het_sequences / _packed_device).  device_ptrs = 0: words / word_off /
@@ -1387,74 +1379,42 @@ int find_del_run(const mtg_index* idx, const uint64_t* words, size_t nwords, con
 int find_het_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, const uint64_t* rep,
                  int max_repeat, int branching_filter, mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_het_stats* st)
 {
-    if (int rc = use_device_of(idx)) return rc;
-    if (!idx || !idx->dev.bloom.bits) { set_error("the index has no Bloom filter (MTG_BLOOM_BITS=0)"); return MTG_ERR_ARG; }
-    *n_calls = 0;
-    if (st) *st = mtg_find_het_stats{};
-    if (nseq == 0) return MTG_OK;
-    const int k = idx->dev.k;
-    if (max_repeat > k - 2) max_repeat = k - 2;
-    SeqInput in;
-    DevBuf d_v, d_p, d_in2, d_out2, d_br, d_cnt, d_before, d_c, d_e, d_mark, d_blk_cnt, d_blk_before, d_sel, d_calls;
-    if (device_ptrs) in.take(words, word_off, len, nseq, bad, rep);
-    else if (int rc = in.upload(words, nwords, word_off, len, nseq, bad, rep)) return rc;
-    if (int rc = in.plane_words(&nwords)) return rc;
-    HIP_TRY(d_v.alloc(nwords * 8)); HIP_TRY(d_p.alloc(nwords * 8)); HIP_TRY(d_in2.alloc(nwords * 8)); HIP_TRY(d_out2.alloc(nwords * 8)); HIP_TRY(d_br.alloc(nwords * 8));
-    HIP_TRY(d_cnt.alloc(nseq * 4)); HIP_TRY(d_before.alloc(nseq * 8));
-    HIP_TRY(d_c.alloc(CNT_HET_SLOTS * 8));
-    HIP_TRY(hipMemset(d_c.p, 0, CNT_HET_SLOTS * 8));
-    unsigned long long* cnt = d_c.as<unsigned long long>();
-    EventSet events;
-    hipEvent_t ev[4];
-    for (hipEvent_t& e : ev) HIP_TRY(events.make(e));
-    const dim3 grid((unsigned)std::min<size_t>(nseq, 256 * 16));
-    unsigned long long c[CNT_HET_SLOTS];
-    float ms = 0, part = 0;
+    FindStage S;
+    if (int rc = S.begin(idx, words, nwords, word_off, len, nseq, bad, rep, true, max_repeat, n_calls, st, device_ptrs); rc || nseq == 0) return rc;
+    const int k = S.k;
+    max_repeat = S.max_repeat;
+    const SeqInput& in = S.in;
+    DevBuf d_e, d_mark;
+    const dim3 grid = S.grid();
+    unsigned long long* cnt = S.cnt();
+    uint64_t *const d_v = S.d_v.as<uint64_t>(), *const d_in2 = S.d_in2.as<uint64_t>(), *const d_out2 = S.d_out2.as<uint64_t>(), *const d_br = S.d_br.as<uint64_t>();
+    uint64_t n_cand = 0, total = 0;
     /* 1. the planes, the candidates counted */
-    HIP_TRY(hipEventRecord(ev[0], 0));
-    hipLaunchKernelGGL(k_profile<true>, grid, dim3(SCAN_TILE), 0, 0, idx->dev, in.words, in.word_off, in.len, nseq, in.bad, (const uint64_t*)nullptr, (uint32_t*)nullptr, d_v.as<uint64_t>(), d_p.as<uint64_t>(), cnt,
-                       d_in2.as<uint64_t>(), d_out2.as<uint64_t>(), d_br.as<uint64_t>());
-    hipLaunchKernelGGL(k_het_count, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_in2.as<uint64_t>(), d_out2.as<uint64_t>(), in.rep, in.word_off, in.len, nseq, k, max_repeat, d_cnt.as<uint32_t>());
-    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_cnt.as<uint32_t>(), nseq, d_before.as<uint64_t>(), cnt + CNT_HET_LISTED);
-    HIP_TRY(hipEventRecord(ev[1], 0));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
-    HIP_TRY(hipEventElapsedTime(&part, ev[0], ev[1])); ms += part;
-    const uint64_t n_cand = c[CNT_HET_LISTED];
-    if (n_cand > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 candidates"); return MTG_ERR_ARG; }
-    uint64_t total = 0;
+    if (int rc = S.planes<true>([&] { hipLaunchKernelGGL(k_het_count, grid, dim3(RUNS_BLOCK), 0, 0, d_v, d_in2, d_out2, in.rep, in.word_off, in.len, nseq, k, max_repeat, S.d_cnt.as<uint32_t>()); },
+                                CNT_HET_LISTED, "candidates", &n_cand)) return rc;
     if (n_cand) {
         /* 2. the candidates listed and judged, the chains resolved, the calls listed in order and written */
         HIP_TRY(d_e.alloc((size_t)n_cand * sizeof(HetEntry)));
         HIP_TRY(hipMemset(d_e.p, 0, (size_t)n_cand * sizeof(HetEntry)));
         HIP_TRY(d_mark.alloc((size_t)n_cand * 4));
         const unsigned cb = (unsigned)((n_cand + RUNS_BLOCK - 1) / RUNS_BLOCK);
-        HIP_TRY(hipEventRecord(ev[2], 0));
-        hipLaunchKernelGGL(k_het_list, grid, dim3(RUNS_BLOCK), 0, 0, d_v.as<uint64_t>(), d_in2.as<uint64_t>(), d_out2.as<uint64_t>(), in.rep, in.word_off, in.len, nseq, k, max_repeat, d_before.as<uint64_t>(),
-                           d_e.as<HetEntry>(), n_cand);
-        hipLaunchKernelGGL(k_het_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, in.words, in.word_off, in.len, in.bad, d_v.as<uint64_t>(), d_out2.as<uint64_t>(),
-                           d_br.as<uint64_t>(), in.rep, d_e.as<HetEntry>(), n_cand, max_repeat, branching_filter, cnt);
-        hipLaunchKernelGGL(k_het_chain, dim3(cb), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), n_cand, d_v.as<uint64_t>(), in.word_off, max_repeat);
-        hipLaunchKernelGGL(k_het_final, dim3(cb), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), n_cand, d_v.as<uint64_t>(), in.word_off, max_repeat, d_mark.as<uint32_t>(), cnt);
-        if (int rc = mark_compact(d_mark.as<uint32_t>(), n_cand, d_blk_cnt, d_blk_before, cnt + CNT_HET_CALLS, d_sel, cap, &total)) return rc;
-        const uint64_t keep = std::min<uint64_t>(total, cap);
-        mtg_find_call* pc = calls;
-        if (keep) {
-            if (!device_ptrs) { HIP_TRY(d_calls.alloc((size_t)keep * sizeof(mtg_find_call))); pc = d_calls.as<mtg_find_call>(); }
-            hipLaunchKernelGGL(k_het_emit, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), d_sel.as<uint32_t>(), keep, pc);
-        }
-        HIP_TRY(hipEventRecord(ev[3], 0));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventSynchronize(ev[3]));
-        if (keep && !device_ptrs) HIP_TRY(hipMemcpy(calls, pc, (size_t)keep * sizeof(mtg_find_call), hipMemcpyDeviceToHost));
-        HIP_TRY(hipEventElapsedTime(&part, ev[2], ev[3])); ms += part;
-        HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
+        HIP_TRY(hipEventRecord(S.e_tail[0], 0));
+        hipLaunchKernelGGL(k_het_list, grid, dim3(RUNS_BLOCK), 0, 0, d_v, d_in2, d_out2, in.rep, in.word_off, in.len, nseq, k, max_repeat, S.d_before.as<uint64_t>(), d_e.as<HetEntry>(), n_cand);
+        hipLaunchKernelGGL(k_het_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, in.words, in.word_off, in.len, in.bad, d_v, d_out2, d_br, in.rep,
+                           d_e.as<HetEntry>(), n_cand, max_repeat, branching_filter, cnt);
+        hipLaunchKernelGGL(k_het_chain, dim3(cb), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), n_cand, d_v, in.word_off, max_repeat);
+        hipLaunchKernelGGL(k_het_final, dim3(cb), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), n_cand, d_v, in.word_off, max_repeat, d_mark.as<uint32_t>(), cnt);
+        if (int rc = S.calls_tail(d_mark.as<uint32_t>(), n_cand, CNT_HET_CALLS, calls, cap, &total, [&](const uint32_t* sel, uint64_t keep, mtg_find_call* out) {
+                hipLaunchKernelGGL(k_het_emit, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), sel, keep, out);
+            })) return rc;
+        if (int rc = S.read_counters()) return rc;
     }
     *n_calls = (size_t)total;
     if (st) {
+        const unsigned long long* c = S.c;
         st->n_positions = c[CNT_POSITIONS]; st->n_candidates = c[CNT_HET_CANDIDATES]; st->n_raw_sites = c[CNT_HET_RAW_SITES]; st->n_filtered = c[CNT_HET_FILTERED]; st->n_suppressed = c[CNT_HET_SUPPRESSED];
         st->n_het_clean = c[CNT_HET_CLEAN]; st->n_het_fuzzy = c[CNT_HET_FUZZY]; st->n_het_small = c[CNT_HET_SMALL];
-        st->kernel_ms = (double)ms;
+        st->kernel_ms = (double)S.ms;
     }
     return MTG_OK;
 }

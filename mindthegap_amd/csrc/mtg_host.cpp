@@ -1880,26 +1880,31 @@ int mtg_index_scan_sequences(const mtg_index* idx, const char* const* seqs, size
 }
 
 /* The scan's packing of strings, and next to it one bit per character that is no nucleotide (the device tells which k-mers cover one):
- * word offsets, lengths, the offset of every sequence's first position, the two word arrays.  Returns false (error set) on a bad argument. */
-static bool pack_with_bad_bits(const char* const* seqs, size_t nseq, int k, uint32_t* const* out, std::vector<uint64_t>& off, std::vector<uint32_t>& len, std::vector<uint64_t>& pos_off,
-                               uint64_t& npos, std::vector<uint64_t>& words, std::vector<uint64_t>& bad)
+ * word offsets, lengths, the offset of every sequence's first position, the two word arrays */
+struct PackedSeqs {
+    std::vector<uint64_t> off, pos_off, words, bad;
+    std::vector<uint32_t> len;
+    uint64_t npos = 0;
+};
+/* Returns false (error set) on a bad argument. */
+static bool pack_with_bad_bits(const char* const* seqs, size_t nseq, int k, uint32_t* const* out, PackedSeqs& P)
 {
-    off.assign(nseq, 0); pos_off.assign(nseq, 0); len.assign(nseq, 0);
+    P.off.assign(nseq, 0); P.pos_off.assign(nseq, 0); P.len.assign(nseq, 0);
     uint64_t nw = 0;
-    npos = 0;
+    P.npos = 0;
     for (size_t s = 0; s < nseq; s++) {
         if (!seqs[s] || (out && !out[s] && strlen(seqs[s]) >= (size_t)k)) { mtgi::set_error("sequence %zu: null pointer", s); return false; }
         const size_t l = strlen(seqs[s]);
         if (l > 0xFFFFFFFFull) { mtgi::set_error("sequence %zu: longer than 2^32 - 1", s); return false; }
-        len[s] = (uint32_t)l; off[s] = nw; nw += (len[s] + 31) / 32 + 2;
-        pos_off[s] = npos; npos += len[s] < (uint32_t)k ? 0 : len[s] - (uint32_t)k + 1;
+        P.len[s] = (uint32_t)l; P.off[s] = nw; nw += (P.len[s] + 31) / 32 + 2;
+        P.pos_off[s] = P.npos; P.npos += P.len[s] < (uint32_t)k ? 0 : P.len[s] - (uint32_t)k + 1;
     }
-    words.assign(nw + 2, 0); bad.assign(nw + 2, 0);
+    P.words.assign(nw + 2, 0); P.bad.assign(nw + 2, 0);
     for (size_t s = 0; s < nseq; s++)
-        for (uint32_t i = 0; i < len[s]; i++) {
+        for (uint32_t i = 0; i < P.len[s]; i++) {
             const unsigned char ch = (unsigned char)seqs[s][i];
-            words[off[s] + (i >> 5)] |= (uint64_t)nt_code(ch) << (2 * (i & 31));
-            if (mtgi::nt_bad(ch)) bad[off[s] + (i >> 6)] |= 1ull << (i & 63);
+            P.words[P.off[s] + (i >> 5)] |= (uint64_t)nt_code(ch) << (2 * (i & 31));
+            if (mtgi::nt_bad(ch)) P.bad[P.off[s] + (i >> 6)] |= 1ull << (i & 63);
         }
     return true;
 }
@@ -1908,18 +1913,15 @@ int mtg_index_profile_sequences(const mtg_index* idx, const char* const* seqs, s
                                 mtg_profile_stats* st)
 {
     if (!idx || !n_runs || (nseq && !seqs) || (runs_cap && !runs)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
-    const int k = idx->dev.k;
-    std::vector<uint64_t> off, pos_off, words, bad;
-    std::vector<uint32_t> len;
-    uint64_t npos = 0;
-    if (!pack_with_bad_bits(seqs, nseq, k, out, off, len, pos_off, npos, words, bad)) return MTG_ERR_ARG;
-    std::vector<uint32_t> flat(out ? npos : 0);
-    int rc = mtgi::profile_run(idx, words.data(), words.size(), off.data(), len.data(), nseq, bad.data(), pos_off.data(), npos, out ? flat.data() : nullptr, runs, runs_cap, n_runs, 0, st);
+    PackedSeqs P;
+    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, out, P)) return MTG_ERR_ARG;
+    std::vector<uint32_t> flat(out ? P.npos : 0);
+    int rc = mtgi::profile_run(idx, P.words.data(), P.words.size(), P.off.data(), P.len.data(), nseq, P.bad.data(), P.pos_off.data(), P.npos, out ? flat.data() : nullptr, runs, runs_cap, n_runs, 0, st);
     if (rc) return rc;
     if (out)
         for (size_t s = 0; s < nseq; s++) {
-            const uint64_t n = (s + 1 < nseq ? pos_off[s + 1] : npos) - pos_off[s];
-            if (n) memcpy(out[s], flat.data() + pos_off[s], n * 4);
+            const uint64_t n = (s + 1 < nseq ? P.pos_off[s + 1] : P.npos) - P.pos_off[s];
+            if (n) memcpy(out[s], flat.data() + P.pos_off[s], n * 4);
         }
     return MTG_OK;
 }
@@ -1930,68 +1932,65 @@ int mtg_index_profile_packed_device(const mtg_index* idx, const uint64_t* d_word
     return mtgi::profile_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, d_pos_off, 0, d_out, d_runs, runs_cap, n_runs, 1, st);
 }
 
+/* the argument checks of the six find entries; have_input: the input arrays that nseq asks for are there */
+static int find_check_args(const mtg_index* idx, bool have_input, int max_repeat, const mtg_find_call* calls, size_t cap, const size_t* n_calls)
+{
+    if (!idx || !n_calls || !have_input || (cap && !calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
+    return MTG_OK;
+}
+
 int mtg_index_find_homo_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_stats* st)
 {
-    if (!idx || !n_calls || (nseq && !seqs) || (cap && !calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
-    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
-    std::vector<uint64_t> off, pos_off, words, bad;
-    std::vector<uint32_t> len;
-    uint64_t npos = 0;
-    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, off, len, pos_off, npos, words, bad)) return MTG_ERR_ARG;
-    return mtgi::find_homo_run(idx, words.data(), words.size(), off.data(), len.data(), nseq, bad.data(), max_repeat, calls, cap, n_calls, 0, st);
+    if (int rc = find_check_args(idx, !nseq || seqs, max_repeat, calls, cap, n_calls)) return rc;
+    PackedSeqs P;
+    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, P)) return MTG_ERR_ARG;
+    return mtgi::find_homo_run(idx, P.words.data(), P.words.size(), P.off.data(), P.len.data(), nseq, P.bad.data(), max_repeat, calls, cap, n_calls, 0, st);
 }
 int mtg_index_find_homo_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
                                       mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_stats* st)
 {
-    if (!idx || !n_calls || (nseq && (!d_words || !d_word_off || !d_len)) || (cap && !d_calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
-    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
+    if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), max_repeat, d_calls, cap, n_calls)) return rc;
     return mtgi::find_homo_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, d_calls, cap, n_calls, 1, st);
 }
 
 int mtg_index_find_del_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_del_stats* st)
 {
-    if (!idx || !n_calls || (nseq && !seqs) || (cap && !calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
-    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
-    std::vector<uint64_t> off, pos_off, words, bad;
-    std::vector<uint32_t> len;
-    uint64_t npos = 0;
-    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, off, len, pos_off, npos, words, bad)) return MTG_ERR_ARG;
-    return mtgi::find_del_run(idx, words.data(), words.size(), off.data(), len.data(), nseq, bad.data(), max_repeat, calls, cap, n_calls, 0, st);
+    if (int rc = find_check_args(idx, !nseq || seqs, max_repeat, calls, cap, n_calls)) return rc;
+    PackedSeqs P;
+    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, P)) return MTG_ERR_ARG;
+    return mtgi::find_del_run(idx, P.words.data(), P.words.size(), P.off.data(), P.len.data(), nseq, P.bad.data(), max_repeat, calls, cap, n_calls, 0, st);
 }
 int mtg_index_find_del_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
                                      mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_del_stats* st)
 {
-    if (!idx || !n_calls || (nseq && (!d_words || !d_word_off || !d_len)) || (cap && !d_calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
-    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
+    if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), max_repeat, d_calls, cap, n_calls)) return rc;
     return mtgi::find_del_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, d_calls, cap, n_calls, 1, st);
 }
 
 int mtg_index_find_het_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, const uint8_t* const* repeated, int max_repeat, int branching_filter, mtg_find_call* calls,
                                  size_t cap, size_t* n_calls, mtg_find_het_stats* st)
 {
-    if (!idx || !n_calls || (nseq && !seqs) || (cap && !calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
-    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
+    if (int rc = find_check_args(idx, !nseq || seqs, max_repeat, calls, cap, n_calls)) return rc;
     const int k = idx->dev.k;
-    std::vector<uint64_t> off, pos_off, words, bad, rep;
-    std::vector<uint32_t> len;
-    uint64_t npos = 0;
-    if (!pack_with_bad_bits(seqs, nseq, k, nullptr, off, len, pos_off, npos, words, bad)) return MTG_ERR_ARG;
+    PackedSeqs P;
+    std::vector<uint64_t> rep;
+    if (!pack_with_bad_bits(seqs, nseq, k, nullptr, P)) return MTG_ERR_ARG;
     if (repeated) { /* the repeat plane: one bit per (k-1)-mer position, at the sequence's word offset */
-        rep.assign(words.size(), 0);
+        rep.assign(P.words.size(), 0);
         for (size_t s = 0; s < nseq; s++) {
-            if (len[s] < (uint32_t)k) continue;
+            if (P.len[s] < (uint32_t)k) continue;
             if (!repeated[s]) { mtgi::set_error("sequence %zu: null repeat flags", s); return MTG_ERR_ARG; }
-            for (uint32_t q = 0; q < len[s] - (uint32_t)k + 2u; q++)
-                if (repeated[s][q]) rep[off[s] + (q >> 6)] |= 1ull << (q & 63);
+            for (uint32_t q = 0; q < P.len[s] - (uint32_t)k + 2u; q++)
+                if (repeated[s][q]) rep[P.off[s] + (q >> 6)] |= 1ull << (q & 63);
         }
     }
-    return mtgi::find_het_run(idx, words.data(), words.size(), off.data(), len.data(), nseq, bad.data(), repeated ? rep.data() : nullptr, max_repeat, branching_filter, calls, cap, n_calls, 0, st);
+    return mtgi::find_het_run(idx, P.words.data(), P.words.size(), P.off.data(), P.len.data(), nseq, P.bad.data(), repeated ? rep.data() : nullptr, max_repeat, branching_filter, calls, cap, n_calls, 0, st);
 }
 int mtg_index_find_het_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, const uint64_t* d_repeat_bits,
                                      int max_repeat, int branching_filter, mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_het_stats* st)
 {
-    if (!idx || !n_calls || (nseq && (!d_words || !d_word_off || !d_len)) || (cap && !d_calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
-    if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
+    if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), max_repeat, d_calls, cap, n_calls)) return rc;
     return mtgi::find_het_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, d_repeat_bits, max_repeat, branching_filter, d_calls, cap, n_calls, 1, st);
 }
 

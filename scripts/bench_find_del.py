@@ -1,4 +1,4 @@
-"""Rate of `find` for homozygous deletions (the planes and gaps of find_homo, then k_del_mark, k_del_judge, k_del_emit) next to `find` for
+"""Rate of `find` for homozygous deletions (the planes and gaps of find_homo, then the deletion observer's k_gap_mark, k_del_judge, k_gap_emit) next to `find` for
 homozygous insertions, on bench_find.py's input with one change: in the scanned copy of every sequence the 32 nucleotides of word 40 are
 replaced, so that each sequence has one gap of 62 positions with both anchors -- a candidate of the deletion observer (judged: no deletion,
 the joined text is not in the graph) and, being longer than k - 1, none of the insertion observers.  Alternating rounds of find_homo /
