@@ -224,6 +224,31 @@ int mtg_index_find_del_sequences(const mtg_index* idx, const char* const* seqs, 
 int mtg_index_find_del_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
                                      mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_del_stats* st);
 
+/* `find` for isolated homozygous SNPs: the reference's gap observer FindSoloSNP (src/FindSNP.hpp:297-355 with snp_at_end, :139-208) and no
+ * other, on the gaps of mtg_index_find_homo_sequences.  A reported gap of exactly k positions from `start` with a valid k-mer right before it:
+ * its k k-mers are those that cover the position g = start + k - 1.  With ref the nucleotide at g, the call is the first of the other three
+ * nucleotides in the order A, C, T, G for which all k k-mers, g replaced by it, are in the graph; with none there is no call.  The observer
+ * leaves the scan alone.  (In the reference a call also corrects the k-mer history that the heterozygous observer reads: not done, the
+ * heterozygous entry knows nothing of these calls.)  FindMultiSNP and FindMultiSNPrev, which take the longer gaps, are not built.  Records as above:
+ *   kind   5 SNP
+ *   pos    g, 0-based (the VCF's POS is pos + 1);  repeat = 0
+ *   left, right   start - 1 and start + k, the positions of the two k-mers
+ *   ins    ALT's ASCII code in bits 0-7, REF's in bits 8-15, both upper case whatever the text's case is
+ * in the order of the scan (ascending seq, then right).  In a combined run the reference asks this observer before the deletion observer: a
+ * gap it calls is not seen by the others (the tool drops deletion calls with the same (seq, left); an insertion candidate is shorter than k).
+ * max_repeat plays no part in the rule and is checked as elsewhere; cap, *n_calls, calls, st and the character rule as for
+ * mtg_index_find_homo_sequences. */
+typedef struct mtg_find_snp_stats {
+    uint64_t n_positions, n_gaps /* calls of the gap observers */, n_candidates /* of those, both k-mers valid and L = k */, n_calls;
+    double kernel_ms;
+    uint64_t reserved[3]; /* (the size of mtg_find_del_stats) */
+} mtg_find_snp_stats;
+int mtg_index_find_snp_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls,
+                                 mtg_find_snp_stats* st);
+/* same on 2-bit packed sequences already in DEVICE memory (no invalid positions); d_calls is a device array */
+int mtg_index_find_snp_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
+                                     mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_snp_stats* st);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Gap filling = Filler::gapFillFromSource over a batch of gaps.
  * ---------------------------------------------------------------------------------------------------------- */
@@ -502,14 +527,17 @@ int mtg_fill_main_on_index(mtg_index* idx, int argc, const char* const* argv);
  * and prefix.profile.txt, the statistics as `key : value` lines.  Returns 0 / 1; nothing is written unless the whole profile succeeded. */
 int mtg_profile_main(int argc, const char* const* argv);
 /* `MindTheGap find (-in reads | -graph container) -ref genome.fa (-homo-insertions | -hete-only | -insert-only | -deletion-only | -homo-only
- * -no-snp | -no-snp) [-max-rep 5] [-het-max-occ 1] [-branching-filter 15] [-kmer-size -abundance-min -abundance-max] [-out prefix]`: the part
+ * -no-snp | -no-snp | -solo-snps | -homo-only -solo-snps) [-max-rep 5] [-het-max-occ 1] [-branching-filter 15] [-kmer-size -abundance-min -abundance-max] [-out prefix]`: the part
  * of the reference's `find` that mtg_index_find_homo_sequences (-homo-insertions), mtg_index_find_het_sequences plus the homozygous insertions
  * of 1-2 nt (-hete-only, as the reference's option of that name) or both in full (-insert-only, calls merged in detection order) cover, and with
  * mtg_index_find_del_sequences the reference's -deletion-only (deletions and the homozygous insertions of 1-2 nt), -homo-only -no-snp (those and
  * the homozygous sites) and -no-snp (all three layers: its default find minus the SNP observers); an insertion call on a gap that the deletion
- * observer calls is dropped, as the reference asks that observer first.  The repeat flags of the heterozygous
+ * observer calls is dropped, as the reference asks that observer first.  -solo-snps (mtg_index_find_snp_sequences alone) and -homo-only -solo-snps
+ * (that observer ahead of the deletion observer and the four homozygous insertion observers; a deletion call on a gap it calls is dropped) are
+ * not configurations of the reference, which has no way to run FindSoloSNP without its multi-SNP observers; they are refused together with
+ * anything that runs the heterozygous observer.  A SNP is one VCF line of writeVcfVariant's form (TYPE=SNP;LEN=1;FUZZY=0).  The repeat flags of the heterozygous
  * observer come from an index of the genome file at k - 1 with abundance_min = het_max_occ + 1 (k >= 12).  Any other combination of these flags
- * stops with a message that names what is not built (SNPs, -bed) and returns 1.  Writes prefix.breakpoints (writeBreakpoint,
+ * stops with a message that names what is not built (the SNPs of longer gaps, -snp-only, the default find, -bed) and returns 1.  Writes prefix.breakpoints (writeBreakpoint,
  * src/FindBreakpoints.hpp:640-658) and prefix.othervariants.vcf (header of src/Finder.cpp:513-541, records of writeIndel and, for deletions,
  * writeVcfVariant: REF = the genome's text from pos over del_size + 1 characters as it stands, ALT its first); ids bkptN count
  * from 1 in detection order across both files; the REPEATED field stays empty (the reference fills it from a Bloom filter of the genome's

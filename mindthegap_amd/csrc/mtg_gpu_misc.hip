@@ -17,6 +17,7 @@
 #include "mtg_find_gaps.h"
 #include "mtg_find_het.h"
 #include "mtg_find_del.h"
+#include "mtg_find_snp.h"
 
 namespace mtgi {
 
@@ -325,6 +326,7 @@ enum { CNT_RUNS = 4, CNT_RUNS_LONGEST, CNT_PROFILE_SLOTS = 8 };
 enum { CNT_GAPS = 4, CNT_GAPS_LONGEST, CNT_GAP_CANDIDATES, CNT_GAP_CALLS, CNT_GAPS_SEEN, CNT_FIND_SLOTS = 16 }; /* (CNT_GAPS: gaps of any kind) */
 enum { CNT_HOMO_CLEAN = 10, CNT_HOMO_FUZZY, CNT_SMALL_CLEAN, CNT_SMALL_FUZZY };
 enum { CNT_DEL_CLEAN = 10, CNT_DEL_FUZZY, CNT_DEL_FALLBACK };
+enum { CNT_SNP_SOLO = 10 };
 enum { CNT_HET_LISTED = 4, CNT_HET_CALLS = 6, CNT_HET_CANDIDATES = 8, CNT_HET_RAW_SITES, CNT_HET_FILTERED, CNT_HET_SUPPRESSED, CNT_HET_CLEAN, CNT_HET_FUZZY, CNT_HET_SMALL };
 
 /* profile along packed sequences: the tile of k_scan (scan_tile_stage: the tile's m-mers hashed once in LDS, Bloom blocks staged by coalesced
@@ -495,7 +497,7 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_profile_finish(mtg_run* runs, ui
 }
 
 /* ---- `find` over the gaps of the scan (include/mtg_fill.h: mtg_index_find_homo_sequences, mtg_index_find_del_sequences).  The gaps come from
- * k_profile_count<true> / k_profile_write<true> as mtg_run records (flags: mtg_find_gaps.h).  An Observer (HomoObserver, DelObserver below) is
+ * k_profile_count<true> / k_profile_write<true> as mtg_run records (flags: mtg_find_gaps.h).  An Observer (HomoObserver, DelObserver, SoloObserver below) is
  * one kind of call on a gap: its candidate test, its judge kernel, the record of a call and its statistics.
  * k_gap_mark: one thread per gap, the observer's candidate test alone -- mark[i] = the gap is a candidate; CNT_GAPS_SEEN += gaps the observers see.
  * k_mark_count / k_profile_seq_scan / k_mark_index: the indices of the non-zero marks in ascending order (counts per workgroup, their
@@ -704,6 +706,69 @@ struct DelObserver {
     {
         st.n_positions = c[CNT_POSITIONS]; st.n_gaps = c[CNT_GAPS_SEEN]; st.n_candidates = n_cand;
         st.n_del_clean = c[CNT_DEL_CLEAN]; st.n_del_fuzzy = c[CNT_DEL_FUZZY]; st.n_fallback = c[CNT_DEL_FALLBACK]; st.n_calls = total;
+    }
+};
+
+/* ---- `find` for isolated homozygous SNPs (include/mtg_fill.h: mtg_index_find_snp_sequences; the rule: mtg_find_snp.h).  The gaps are those of
+ * the other gap observers, marked, listed and emitted by the same kernels for SoloObserver. */
+/* The observer on one candidate gap, one wave each (four to a workgroup): a gap of k positions from `start`, both k-mers anchors, so the text
+ * [start - 1, start + 2k) lies in the sequence and holds nucleotides only.  The at most three packed words of [start, start + 2k - 1) are
+ * loaded uniformly; lane l takes window j = l % 32 (< k) of the k-mer at start + j (Bloom filter, then the table).  Two alternatives side by
+ * side -- lanes 0-31 the first in A, C, T, G order, lanes 32-63 the second -- then the third in lanes 0-31, not looked at when one of the
+ * first two holds: the order is fixed.  res[c] = 0: no call; else SNP_CALLED | alt << SNP_ALT_SHIFT | ref << SNP_REF_SHIFT.
+ * CNT_SNP_SOLO += 1 per call */
+__global__ void __launch_bounds__(FIND_WAVES * 64) k_snp_judge(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off, const mtg_run* __restrict__ gaps,
+                                                               const uint32_t* __restrict__ cand, uint64_t ncand, uint32_t* res, unsigned long long* counters)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t c = (uint64_t)blockIdx.x * FIND_WAVES + (threadIdx.x >> 6);
+    if (c >= ncand) return; /* (uniform in the wave; the kernel has no workgroup barrier) */
+    const mtg_run g = gaps[cand[c]];
+    const int k = ix.k;
+    const uint64_t* w = words + word_off[g.seq] + (g.start >> 5);
+    const uint32_t nw = snp_text_words(g.start, k), rel0 = g.start & 31u;
+    const uint64_t t0 = w[0], t1 = nw > 1u ? w[1] : 0ull, t2 = nw > 2u ? w[2] : 0ull;
+    const uint32_t ref = (uint32_t)(snp_text_kmer(t0, t1, t2, rel0, k) >> (2 * (k - 1))) & 3u;
+    const uint32_t half = lane >> 5, j = lane & 31u;
+    const bool mine = j < (uint32_t)k;
+    const uint64_t km = mine ? snp_text_kmer(t0, t1, t2, rel0 + j, k) : 0ull, cmpl = 0xAAAAAAAAAAAAAAAAULL & kmask(k);
+    uint32_t lines = 0;
+    int alt = -1;
+    for (uint32_t it = 0; it < 2u && alt < 0; it++) {
+        bool solid = true;
+        if (mine && 2u * it + half < 3u) {
+            Kmer x;
+            x.r = snp_window(km, (int)j, k, snp_alt(ref, 2u * it + half)) ^ cmpl;
+            x.f = revcomp(x.r, k);
+            solid = bloom_test(ix.bloom, x, k) && abundance(ix, x, lines) != 0;
+        }
+        const unsigned long long bal = __ballot(solid);
+        if ((uint32_t)bal == 0xFFFFFFFFu) alt = (int)snp_alt(ref, 2u * it);
+        else if (it == 0 && (uint32_t)(bal >> 32) == 0xFFFFFFFFu) alt = (int)snp_alt(ref, 1u);
+    }
+    if (lane == 0) {
+        res[c] = alt >= 0 ? SNP_CALLED | ((uint32_t)alt << SNP_ALT_SHIFT) | (ref << SNP_REF_SHIFT) : 0u;
+        if (alt >= 0) atomicAdd(&counters[CNT_SNP_SOLO], 1ull);
+    }
+}
+/* the gap observer of the isolated homozygous SNPs: gap_is_snp_candidate (mtg_find_snp.h), k_snp_judge, kind 5 */
+struct SoloObserver {
+    using Stats = mtg_find_snp_stats;
+    static MTG_DEV bool is_candidate(const mtg_run& g, int k, int max_repeat) { return gap_is_snp_candidate(g.length, g.flags, k, max_repeat); }
+    static void judge(const Index& ix, const uint64_t* words, const uint64_t* word_off, const uint32_t*, const uint64_t*, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand,
+                      int, uint32_t* res, unsigned long long* cnt)
+    {
+        hipLaunchKernelGGL(k_snp_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, ix, words, word_off, gaps, cand, n_cand, res, cnt);
+    }
+    static MTG_DEV mtg_find_call call_of(const mtg_run& g, uint32_t o, int k)
+    {
+        mtg_find_call q;
+        q.seq = g.seq; q.pos = snp_pos_of(g.start, k); q.kind = 5u; q.repeat = 0u; q.left = g.start - 1u; q.right = g.start + g.length; q.ins = snp_ins_of(o);
+        return q;
+    }
+    static void fill(Stats& st, const unsigned long long* c, uint64_t n_cand, uint64_t)
+    {
+        st.n_positions = c[CNT_POSITIONS]; st.n_gaps = c[CNT_GAPS_SEEN]; st.n_candidates = n_cand; st.n_calls = c[CNT_SNP_SOLO];
     }
 };
 
@@ -1371,6 +1436,13 @@ int find_del_run(const mtg_index* idx, const uint64_t* words, size_t nwords, con
                  mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_del_stats* st)
 {
     return find_gap_run<DelObserver>(idx, words, nwords, word_off, len, nseq, bad, max_repeat, calls, cap, n_calls, device_ptrs, st);
+}
+
+/* `find` for isolated homozygous SNPs (mtg_index_find_snp_sequences / _packed_device): the gap run with SoloObserver */
+int find_snp_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
+                 mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_snp_stats* st)
+{
+    return find_gap_run<SoloObserver>(idx, words, nwords, word_off, len, nseq, bad, max_repeat, calls, cap, n_calls, device_ptrs, st);
 }
 
 /* `find` for heterozygous insertions over packed sequences (mtg_index_find_het_sequences / _packed_device).  device_ptrs = 0: words / word_off /

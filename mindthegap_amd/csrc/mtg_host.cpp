@@ -142,6 +142,12 @@ __attribute__((weak)) int find_del_run(const mtg_index*, const uint64_t*, size_t
     set_error("this build has no device code for find");
     return MTG_ERR_NO_DEVICE;
 }
+__attribute__((weak)) int find_snp_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, int, mtg_find_call*, size_t, size_t*, int,
+                                       mtg_find_snp_stats*)
+{
+    set_error("this build has no device code for find");
+    return MTG_ERR_NO_DEVICE;
+}
 __attribute__((weak)) int find_het_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, const uint64_t*, int, int, mtg_find_call*, size_t,
                                        size_t*, int, mtg_find_het_stats*)
 {
@@ -1932,7 +1938,7 @@ int mtg_index_profile_packed_device(const mtg_index* idx, const uint64_t* d_word
     return mtgi::profile_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, d_pos_off, 0, d_out, d_runs, runs_cap, n_runs, 1, st);
 }
 
-/* the argument checks of the six find entries; have_input: the input arrays that nseq asks for are there */
+/* the argument checks of the eight find entries; have_input: the input arrays that nseq asks for are there */
 static int find_check_args(const mtg_index* idx, bool have_input, int max_repeat, const mtg_find_call* calls, size_t cap, const size_t* n_calls)
 {
     if (!idx || !n_calls || !have_input || (cap && !calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
@@ -1966,6 +1972,20 @@ int mtg_index_find_del_packed_device(const mtg_index* idx, const uint64_t* d_wor
 {
     if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), max_repeat, d_calls, cap, n_calls)) return rc;
     return mtgi::find_del_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, d_calls, cap, n_calls, 1, st);
+}
+
+int mtg_index_find_snp_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_snp_stats* st)
+{
+    if (int rc = find_check_args(idx, !nseq || seqs, max_repeat, calls, cap, n_calls)) return rc;
+    PackedSeqs P;
+    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, P)) return MTG_ERR_ARG;
+    return mtgi::find_snp_run(idx, P.words.data(), P.words.size(), P.off.data(), P.len.data(), nseq, P.bad.data(), max_repeat, calls, cap, n_calls, 0, st);
+}
+int mtg_index_find_snp_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
+                                     mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_snp_stats* st)
+{
+    if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), max_repeat, d_calls, cap, n_calls)) return rc;
+    return mtgi::find_snp_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, d_calls, cap, n_calls, 1, st);
 }
 
 int mtg_index_find_het_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, const uint8_t* const* repeated, int max_repeat, int branching_filter, mtg_find_call* calls,

@@ -112,8 +112,14 @@ class FindDelStats(C.Structure):
                 ("n_fallback", C.c_uint64), ("n_calls", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
+class FindSnpStats(C.Structure):
+    _fields_ = [("n_positions", C.c_uint64), ("n_gaps", C.c_uint64), ("n_candidates", C.c_uint64), ("n_calls", C.c_uint64), ("kernel_ms", C.c_double),
+                ("reserved", C.c_uint64 * 3)]
+
+
 # a call of `find` (mtg_find_call): kind 0 = homozygous insertion site, 1 = homozygous insertion of 1-2 nt, 2 = heterozygous site,
-# 3 = heterozygous insertion of 1-2 nt, 4 = homozygous deletion; ins indexes FIND_INSERTIONS (kinds 1 and 3) or is the deleted length (kind 4)
+# 3 = heterozygous insertion of 1-2 nt, 4 = homozygous deletion, 5 = isolated homozygous SNP; ins indexes FIND_INSERTIONS (kinds 1 and 3), is the
+# deleted length (kind 4) or holds ALT's ASCII code in bits 0-7 and REF's in bits 8-15 (kind 5)
 CALL_DTYPE = np.dtype([("seq", np.uint32), ("pos", np.uint32), ("kind", np.uint32), ("repeat", np.uint32), ("left", np.uint32), ("right", np.uint32), ("ins", np.uint32)])
 FIND_INSERTIONS = ("A", "C", "G", "T", "AA", "AC", "AG", "AT", "CA", "CC", "CG", "CT", "GA", "GC", "GG", "GT", "TA", "TC", "TG", "TT")
 
@@ -227,6 +233,8 @@ def _bind(lib):
     lib.mtg_index_find_homo_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindStats)]
     lib.mtg_index_find_del_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindDelStats)]
     lib.mtg_index_find_del_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindDelStats)]
+    lib.mtg_index_find_snp_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindSnpStats)]
+    lib.mtg_index_find_snp_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindSnpStats)]
     lib.mtg_index_find_het_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindHetStats)]
     lib.mtg_index_find_het_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t),
                                                      P(FindHetStats)]
@@ -596,6 +604,28 @@ class Index:
         total, st = C.c_size_t(), FindDelStats()
         _check(self.lib.mtg_index_find_del_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap, C.byref(total), C.byref(st)))
         return total.value, {f[0]: getattr(st, f[0]) for f in FindDelStats._fields_}
+
+    def find_snp_sequences(self, seqs, max_repeat=5, cap=None):
+        """`find` for isolated homozygous SNPs (kind 5: pos = the SNP's position, ins = ALT's ASCII code | REF's << 8) of seqs against the graph;
+        returns (calls as a CALL_DTYPE array in the order of the scan, stats dict).  cap as in find_homo_sequences."""
+        n = len(seqs)
+        arr = (C.c_char_p * n)(*[s.encode() for s in seqs])
+        room = 1024 if cap is None else int(cap)
+        while True:
+            calls = np.zeros(room, dtype=CALL_DTYPE)
+            total, st = C.c_size_t(), FindSnpStats()
+            _check(self.lib.mtg_index_find_snp_sequences(self.h, arr, n, max_repeat, calls.ctypes.data if room else None, room, C.byref(total), C.byref(st)))
+            if cap is not None or total.value <= room:
+                break
+            room = total.value
+        stats = {f[0]: getattr(st, f[0]) for f in FindSnpStats._fields_[:5]}
+        return calls[:min(total.value, room)], stats
+
+    def find_snp_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap):
+        """the same on packed sequences in device memory (pointers as integers; calls_ptr: device array of cap mtg_find_call); returns (total calls, stats dict)"""
+        total, st = C.c_size_t(), FindSnpStats()
+        _check(self.lib.mtg_index_find_snp_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap, C.byref(total), C.byref(st)))
+        return total.value, {f[0]: getattr(st, f[0]) for f in FindSnpStats._fields_[:5]}
 
     def find_het_sequences(self, seqs, repeated=None, max_repeat=5, branching_filter=15, cap=None):
         """`find` for heterozygous insertions: the sites (kind 2) and the insertions of 1-2 nt (kind 3) of seqs against the graph; returns (calls
