@@ -229,7 +229,7 @@ int mtg_index_find_del_packed_device(const mtg_index* idx, const uint64_t* d_wor
  * its k k-mers are those that cover the position g = start + k - 1.  With ref the nucleotide at g, the call is the first of the other three
  * nucleotides in the order A, C, T, G for which all k k-mers, g replaced by it, are in the graph; with none there is no call.  The observer
  * leaves the scan alone.  (In the reference a call also corrects the k-mer history that the heterozygous observer reads: not done, the
- * heterozygous entry knows nothing of these calls.)  FindMultiSNP and FindMultiSNPrev, which take the longer gaps, are not built.  Records as above:
+ * heterozygous entry knows nothing of these calls.)  FindMultiSNP, which takes the longer gaps, is mtg_index_find_msnp_sequences; FindMultiSNPrev is not built.  Records as above:
  *   kind   5 SNP
  *   pos    g, 0-based (the VCF's POS is pos + 1);  repeat = 0
  *   left, right   start - 1 and start + k, the positions of the two k-mers
@@ -248,6 +248,41 @@ int mtg_index_find_snp_sequences(const mtg_index* idx, const char* const* seqs, 
 /* same on 2-bit packed sequences already in DEVICE memory (no invalid positions); d_calls is a device array */
 int mtg_index_find_snp_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
                                      mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_snp_stats* st);
+
+/* `find` for close homozygous SNPs: the reference's gap observer FindMultiSNP (src/FindSNP.hpp:435-564 with snp_at_end, :139-208, and
+ * correct_history) and no other, on the gaps of mtg_index_find_homo_sequences.  A reported gap of L > k + snp_min_val positions from `start`
+ * with a valid k-mer right before it is walked from the left with a cursor c = 0 and a private copy T of its text; while c != L:
+ *   g = start + c + k - 1, ref = T[g]; for each of the other three nucleotides a, f(a) = the number of leading windows j = 0, 1, ..
+ *   < min(k, L - c + 1) in the graph, window j being the k-mer of T at start + c + j with g replaced by a; M = max f.  The winner is the first
+ *   nucleotide in the order A, C, T, G with f = k when M = k, else the last one in that order with f = M.  M < snp_min_val: stop.
+ *   c + M > L: stop.  Else a SNP at g, REF ref, ALT the winner; T[g] = winner (the next step reads the corrected text); c += M.
+ * consumed = the final c: L = the gap is taken, 0 < c < L = in part, 0 = untouched.  (In the reference a gap taken in part reaches the later
+ * observers shortened and with a corrected kmer_begin, and a call corrects the history that the heterozygous observer reads: not done, the
+ * other entries know nothing of these calls.)  DEVIATION: the reference keeps the text in a ring of 256 k-mers addressed by unsigned char;
+ * from L = 255 on the ring has been overwritten and the reference reports positions it did not look at (23 of 29 such gaps of a random
+ * set differ from the rule above).  Gaps of 255 positions and more are not judged: counted in n_long, no call.  FindMultiSNPrev, which
+ * walks a gap from the right, is not built.  Records as above:
+ *   kind   6 SNP of a multi-SNP gap (its VCF line is that of kind 5)
+ *   pos    g, 0-based;  repeat = 0
+ *   left, right   start - 1 and start + L, the positions of the gap's two k-mers, the same for every SNP of the gap
+ *   ins    as for kind 5
+ * in the order of the scan (ascending seq, then gap, then pos).  snp_min_val: 1 .. k (the reference's default is 5), else MTG_ERR_ARG.
+ * gaps (gap_cap records; may be NULL with gap_cap = 0) receives one record per candidate gap in scan order, the long ones with consumed = 0;
+ * *n_gaps (may be NULL) is their total, which can exceed gap_cap as *n_calls can exceed cap.  max_repeat plays no part in the rule and is
+ * checked as elsewhere; cap, *n_calls, calls, st and the character rule as for mtg_index_find_homo_sequences. */
+typedef struct mtg_find_msnp_gap {
+    uint32_t seq, start, length, consumed, n_snps;
+} mtg_find_msnp_gap;
+typedef struct mtg_find_msnp_stats {
+    uint64_t n_positions, n_gaps /* calls of the gap observers */, n_candidates /* of those, both k-mers valid and L > k + snp_min_val */, n_calls;
+    double kernel_ms;
+    uint64_t n_full /* gaps with consumed = L */, n_partial /* 0 < consumed < L */, n_long /* L >= 255: not judged */;
+} mtg_find_msnp_stats;
+int mtg_index_find_msnp_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, int snp_min_val, mtg_find_call* calls, size_t cap, size_t* n_calls,
+                                  mtg_find_msnp_gap* gaps, size_t gap_cap, size_t* n_gaps, mtg_find_msnp_stats* st);
+/* same on 2-bit packed sequences already in DEVICE memory (no invalid positions); d_calls and d_gaps are device arrays */
+int mtg_index_find_msnp_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat, int snp_min_val,
+                                      mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_msnp_gap* d_gaps, size_t gap_cap, size_t* n_gaps, mtg_find_msnp_stats* st);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Gap filling = Filler::gapFillFromSource over a batch of gaps.
@@ -527,7 +562,7 @@ int mtg_fill_main_on_index(mtg_index* idx, int argc, const char* const* argv);
  * and prefix.profile.txt, the statistics as `key : value` lines.  Returns 0 / 1; nothing is written unless the whole profile succeeded. */
 int mtg_profile_main(int argc, const char* const* argv);
 /* `MindTheGap find (-in reads | -graph container) -ref genome.fa (-homo-insertions | -hete-only | -insert-only | -deletion-only | -homo-only
- * -no-snp | -no-snp | -solo-snps | -homo-only -solo-snps) [-max-rep 5] [-het-max-occ 1] [-branching-filter 15] [-kmer-size -abundance-min -abundance-max] [-out prefix]`: the part
+ * -no-snp | -no-snp | -solo-snps | -homo-only -solo-snps | -multi-snps [-snp-min-val 5] | -solo-snps -multi-snps [-snp-min-val 5]) [-max-rep 5] [-het-max-occ 1] [-branching-filter 15] [-kmer-size -abundance-min -abundance-max] [-out prefix]`: the part
  * of the reference's `find` that mtg_index_find_homo_sequences (-homo-insertions), mtg_index_find_het_sequences plus the homozygous insertions
  * of 1-2 nt (-hete-only, as the reference's option of that name) or both in full (-insert-only, calls merged in detection order) cover, and with
  * mtg_index_find_del_sequences the reference's -deletion-only (deletions and the homozygous insertions of 1-2 nt), -homo-only -no-snp (those and
@@ -535,9 +570,12 @@ int mtg_profile_main(int argc, const char* const* argv);
  * observer calls is dropped, as the reference asks that observer first.  -solo-snps (mtg_index_find_snp_sequences alone) and -homo-only -solo-snps
  * (that observer ahead of the deletion observer and the four homozygous insertion observers; a deletion call on a gap it calls is dropped) are
  * not configurations of the reference, which has no way to run FindSoloSNP without its multi-SNP observers; they are refused together with
- * anything that runs the heterozygous observer.  A SNP is one VCF line of writeVcfVariant's form (TYPE=SNP;LEN=1;FUZZY=0).  The repeat flags of the heterozygous
+ * anything that runs the heterozygous observer.  -multi-snps (mtg_index_find_msnp_sequences alone) and -solo-snps -multi-snps (both forward SNP
+ * observers, their lists merged in detection order) are not configurations of the reference either; with any flag that runs the deletion, the
+ * insertion or the heterozygous observers they are refused: a partially consumed gap would reach those shortened and with a corrected kmer_begin,
+ * which is not built.  A SNP is one VCF line of writeVcfVariant's form (TYPE=SNP;LEN=1;FUZZY=0).  The repeat flags of the heterozygous
  * observer come from an index of the genome file at k - 1 with abundance_min = het_max_occ + 1 (k >= 12).  Any other combination of these flags
- * stops with a message that names what is not built (the SNPs of longer gaps, -snp-only, the default find, -bed) and returns 1.  Writes prefix.breakpoints (writeBreakpoint,
+ * stops with a message that names what is not built (the reverse multi-SNP observer, -snp-only, the default find, -bed) and returns 1.  Writes prefix.breakpoints (writeBreakpoint,
  * src/FindBreakpoints.hpp:640-658) and prefix.othervariants.vcf (header of src/Finder.cpp:513-541, records of writeIndel and, for deletions,
  * writeVcfVariant: REF = the genome's text from pos over del_size + 1 characters as it stands, ALT its first); ids bkptN count
  * from 1 in detection order across both files; the REPEATED field stays empty (the reference fills it from a Bloom filter of the genome's

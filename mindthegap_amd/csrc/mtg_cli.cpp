@@ -1464,14 +1464,17 @@ template <typename Entry> static int find_all_calls(std::vector<mtg_find_call>& 
  * `-deletion-only | -homo-only -no-snp | -no-snp`: the reference's configurations of those names (src/Finder.cpp:320-398, :549-582), with the
  * homozygous deletions of mtg_index_find_del_sequences ahead of the insertion observers.  `-solo-snps | -homo-only -solo-snps`, configurations of
  * this tool alone: the isolated homozygous SNPs of mtg_index_find_snp_sequences, alone or ahead of the deletion and the homozygous insertion
- * observers.  Both files are written once the whole scan is there. */
+ * observers.  `-multi-snps | -solo-snps -multi-snps`, also of this tool alone: the close homozygous SNPs of mtg_index_find_msnp_sequences (the
+ * forward multi-SNP observer), alone or with the isolated ones; with any other observer they are refused.  Both files are written once the whole
+ * scan is there. */
 int find_main(int argc, const char* const* argv)
 {
     std::string in, graph, ref, out = "MindTheGap_Expe"; /* the reference names it after the date (src/Finder.cpp: MindTheGap_Expe-<date>) */
-    int k = 31, abundance_min = -1, abundance_max = 0, max_repeat = 5, het_max_occ = 1, branching_filter = 15;
+    int k = 31, abundance_min = -1, abundance_max = 0, max_repeat = 5, het_max_occ = 1, branching_filter = 15, snp_min_val = 5;
     bool homo_flag = false, hete_only = false, insert_only = false, deletion_only = false, homo_only = false, no_snp = false, other_mode = false, solo_snps = false;
+    bool multi_snps = false, min_val_given = false;
     const char* usage = "Usage: MindTheGap find (-in <reads> | -graph <container>) -ref <genome.fa> (-homo-insertions | -hete-only | -insert-only | -deletion-only | -homo-only -no-snp | "
-                        "-no-snp | -solo-snps | -homo-only -solo-snps) [-max-rep 5] [-het-max-occ 1] "
+                        "-no-snp | -solo-snps | -homo-only -solo-snps | -multi-snps [-snp-min-val 5] | -solo-snps -multi-snps [-snp-min-val 5]) [-max-rep 5] [-het-max-occ 1] "
                         "[-branching-filter 15] [-kmer-size 31] [-abundance-min auto] [-abundance-max 0] [-out <prefix>]\n";
     for (int i = 0; i < argc; i++) {
         const std::string a = argv[i];
@@ -1489,6 +1492,8 @@ int find_main(int argc, const char* const* argv)
         else if (a == "-homo-only") homo_only = true;
         else if (a == "-no-snp") no_snp = true;
         else if (a == "-solo-snps") solo_snps = true;
+        else if (a == "-multi-snps") multi_snps = true;
+        else if (a == "-snp-min-val") { ok = val(v); snp_min_val = atoi(v.c_str()); min_val_given = true; }
         else if (a == "-snp-only" || a == "-no-insert" || a == "-no-deletion" || a == "-no-hetero" || a == "-with-backup") other_mode = true; /* refused below, with the message */
         else if (a == "-het-max-occ") { ok = val(v); het_max_occ = atoi(v.c_str()); }
         else if (a == "-branching-filter") { ok = val(v); branching_filter = atoi(v.c_str()); }
@@ -1511,6 +1516,19 @@ int find_main(int argc, const char* const* argv)
     /* -solo-snps, not an option of the reference: the isolated SNPs of FindSoloSNP alone, or with -homo-only ahead of the deletion observer and
      * the four homozygous insertion observers (the reference's -homo-only without its two multi-SNP observers).  Never with the heterozygous
      * observer: in the reference a solo call corrects the k-mer history that observer reads, which is not built */
+    /* -multi-snps, not an option of the reference either: the close SNPs of FindMultiSNP alone, or with -solo-snps both forward SNP observers
+     * (their candidates are disjoint: L = k against L > k + snp_min_val).  Never with an observer that the reference asks after it: a gap
+     * taken in part reaches those shortened and with a corrected kmer_begin, which is not built */
+    if (multi_snps && (other_mode || ins_flags || del_flags)) {
+        fprintf(stderr, "EXCEPTION: -multi-snps (the close homozygous SNPs of the forward multi-SNP observer, not an option of the reference) runs alone or as -solo-snps -multi-snps.  "
+                        "With a flag that runs the deletion, insertion or heterozygous observers (-homo-only, -deletion-only, -no-snp, -homo-insertions, -hete-only, -insert-only) it is "
+                        "refused: a partially consumed gap reaches the later observers shortened and with a corrected kmer_begin, and that is not built.  The reverse multi-SNP "
+                        "observer, -snp-only and the default find are not built either.\n%s", usage);
+        return 1;
+    }
+    if (min_val_given && !multi_snps) { fprintf(stderr, "EXCEPTION: -snp-min-val is accepted with -multi-snps only\n%s", usage); return 1; }
+    if (multi_snps && snp_min_val < 1) { fprintf(stderr, "EXCEPTION: -snp-min-val must be 1 .. k\n"); return 1; }
+    const bool run_multi = multi_snps;
     const bool solo_alone = solo_snps && !other_mode && !ins_flags && !del_flags, solo_homo = solo_snps && !other_mode && !ins_flags && homo_only && !deletion_only && !no_snp;
     const bool run_snp = solo_alone || solo_homo;
     if (solo_snps && !run_snp) {
@@ -1520,8 +1538,8 @@ int find_main(int argc, const char* const* argv)
         return 1;
     }
     const bool run_del = solo_homo || (!solo_snps && !other_mode && !ins_flags && (no_snp ? !deletion_only : deletion_only && !homo_only));
-    const bool known = run_snp || run_del || (!other_mode && ins_flags && !del_flags);
-    const bool run_homo = known && !solo_alone, run_het = known && (hete_only || insert_only || (no_snp && !homo_only)), homo_sites = known && (homo_flag || insert_only || no_snp || solo_homo);
+    const bool known = run_snp || run_multi || run_del || (!other_mode && ins_flags && !del_flags);
+    const bool run_homo = known && !solo_alone && !run_multi, run_het = known && (hete_only || insert_only || (no_snp && !homo_only)), homo_sites = known && (homo_flag || insert_only || no_snp || solo_homo);
     if (!known) {
         fprintf(stderr, "EXCEPTION: this build of find detects insertions (sites and insertions of 1-2 nt) and homozygous deletions: SNPs and -bed are not built, deletions are "
                         "found only under -deletion-only, -homo-only -no-snp or -no-snp, and heterozygous insertions only under -hete-only, -insert-only or -no-snp.  Pass "
@@ -1543,8 +1561,8 @@ int find_main(int argc, const char* const* argv)
     if (rc) { fprintf(stderr, "EXCEPTION: %s\n", mtg_last_error()); return 1; }
     std::vector<const char*> seqs(recs.size());
     for (size_t i = 0; i < recs.size(); i++) seqs[i] = recs[i].second.c_str();
-    std::vector<mtg_find_call> calls(run_homo ? 4096 : 0), het_calls(run_het ? 4096 : 0), del_calls(run_del ? 4096 : 0), snp_calls(run_snp ? 4096 : 0);
-    size_t n_calls = 0, n_het = 0, n_del = 0, n_snp = 0;
+    std::vector<mtg_find_call> calls(run_homo ? 4096 : 0), het_calls(run_het ? 4096 : 0), del_calls(run_del ? 4096 : 0), snp_calls(run_snp ? 4096 : 0), msnp_calls(run_multi ? 4096 : 0);
+    size_t n_calls = 0, n_het = 0, n_del = 0, n_snp = 0, n_msnp = 0;
     mtg_find_stats st{};
     mtg_find_het_stats hst{};
     const time_t t_start = time(0);
@@ -1563,6 +1581,11 @@ int find_main(int argc, const char* const* argv)
     }
     if (run_snp && !rc) {
         rc = find_all_calls(snp_calls, n_snp, [&](mtg_find_call* c, size_t cap, size_t* n) { return mtg_index_find_snp_sequences(idx, seqs.data(), seqs.size(), max_repeat, c, cap, n, nullptr); });
+    }
+    if (run_multi && !rc) {
+        rc = find_all_calls(msnp_calls, n_msnp, [&](mtg_find_call* c, size_t cap, size_t* n) {
+            return mtg_index_find_msnp_sequences(idx, seqs.data(), seqs.size(), max_repeat, snp_min_val, c, cap, n, nullptr, 0, nullptr, nullptr);
+        });
     }
     if (run_het && !rc) {
         /* the repeated (k-1)-mers of the genome (fillRefBloom, src/FindBreakpoints.hpp:956-1008, as an exact set): an index of the genome file at
@@ -1586,7 +1609,20 @@ int find_main(int argc, const char* const* argv)
     const double seconds = difftime(time(0), t_start);
     mtg_index_free(idx);
     if (rc) { fprintf(stderr, "EXCEPTION: %s\n", mtg_last_error()); return 1; }
-    if (run_snp) {
+    if (run_multi) {
+        /* both forward SNP observers are asked at right + 1 of their gap and no gap is a candidate of both: the lists, each in scan order, merge by
+         * (seq, right) into the order of detection; the SNPs of one gap stay together, ascending.  The merged list takes the place of the solo calls */
+        std::vector<mtg_find_call> both;
+        both.reserve(n_snp + n_msnp);
+        size_t i = 0, j = 0;
+        while (i < n_snp || j < n_msnp) {
+            const bool solo_first = i < n_snp && (j >= n_msnp || (snp_calls[i].seq != msnp_calls[j].seq ? snp_calls[i].seq < msnp_calls[j].seq : snp_calls[i].right < msnp_calls[j].right));
+            both.push_back(solo_first ? snp_calls[i++] : msnp_calls[j++]);
+        }
+        snp_calls.swap(both);
+        n_snp = snp_calls.size();
+    }
+    if (run_snp || run_multi) {
         /* the solo observer is asked before the deletion observer: a deletion call on a gap with a solo call -- the same (seq, left) -- is dropped.
          * Both lists are in scan order and both kinds are detected at right + 1; the merged list takes the place of the deletion calls below */
         std::vector<mtg_find_call> first;
@@ -1602,7 +1638,7 @@ int find_main(int argc, const char* const* argv)
         n_del = kept;
     }
     const size_t n_first = n_del + n_snp; /* calls of the observers asked before the insertion observers */
-    if (run_del || run_snp) {
+    if (run_del || run_snp || run_multi) {
         /* the reference asks the deletion observer first and leaves the gap at the first observer that calls it (src/FindBreakpoints.hpp:582-590):
          * an insertion call on a gap with a deletion call -- the same (seq, left) -- is dropped.  Both lists are in scan order; a deletion is
          * detected where a homozygous insertion is (right - repeat + 1 there, right + 1 here), and no gap keeps two calls, so the merge by
@@ -1656,7 +1692,7 @@ int find_main(int argc, const char* const* argv)
         const std::string left = kmer_string(s, c.left);
         const int id = (int)i + 1;
         const bool het = c.kind == 2 || c.kind == 3;
-        if (c.kind == 5) { /* writeVcfVariant as FindSNP.hpp:340-347 calls it: REF and ALT from the 2-bit codes, upper case */
+        if (c.kind == 5 || c.kind == 6) { /* writeVcfVariant as FindSNP.hpp:340-347 and :502-510 call it: REF and ALT from the 2-bit codes, upper case */
             appendf(vcf, "%s\t%lli\tbkpt%i\t%c\t%c\t.\tPASS\tTYPE=SNP;LEN=1;FUZZY=0\tGT\t1/1\n", name.c_str(), (long long)c.pos + 1, id, (int)((c.ins >> 8) & 0xFFu), (int)(c.ins & 0xFFu));
         } else if (c.kind == 4) { /* writeVcfVariant, :661-678, as FindDeletion.hpp:148-160 calls it: the genome's text as it stands */
             const std::string del = s.substr(c.pos, (size_t)c.ins + 1);
@@ -1685,7 +1721,7 @@ int find_main(int argc, const char* const* argv)
     printf("    Breakpoint detection options\n        max_repeat                               : %i\n", max_repeat);
     if (run_het) printf("        hetero_max_occ                           : %i\n        branching filter value                   : %i\n", het_max_occ, branching_filter);
     printf("        homo_insertions                          : %s\n        hete_insertions                          : %s\n        snp                                      : %s\n"
-           "        deletion                                 : %s\n", homo_sites ? "yes" : "no", run_het ? "yes" : "no", run_snp ? "isolated only" : "no", run_del ? "yes" : "no");
+           "        deletion                                 : %s\n", homo_sites ? "yes" : "no", run_het ? "yes" : "no", run_multi ? (run_snp ? "isolated and close (forward)" : "close only (forward)") : run_snp ? "isolated only" : "no", run_del ? "yes" : "no");
     printf("Results\n    Insertion breakpoints\n        homozygous                               : %llu\n            clean                                    : %llu\n"
            "            fuzzy                                    : %llu\n", (unsigned long long)(st.n_homo_clean + st.n_homo_fuzzy), (unsigned long long)st.n_homo_clean, (unsigned long long)st.n_homo_fuzzy);
     if (run_het) printf("        heterozygous                             : %llu\n            clean                                    : %llu\n            fuzzy                                    : %llu\n",
@@ -1694,7 +1730,7 @@ int find_main(int argc, const char* const* argv)
     if (run_del) printf("        deletions                                : %llu\n", (unsigned long long)n_del);
     printf("        Homozygous insertions 1-2 bp size        : %llu\n", (unsigned long long)(st.n_small_clean + st.n_small_fuzzy));
     if (run_het) printf("        Heterozygous insertions 1-2 bp size      : %llu\n", (unsigned long long)hst.n_het_small);
-    if (run_snp) printf("        SNPs                                     : %llu\n", (unsigned long long)n_snp);
+    if (run_snp || run_multi) printf("        SNPs                                     : %llu\n", (unsigned long long)n_snp);
     printf("    Time                                     : %.1f s\n    Output files\n        breakpoint_file                          : %s.breakpoints\n        othervariants_file                       : %s.othervariants.vcf\n",
            seconds, out.c_str(), out.c_str());
     return 0;

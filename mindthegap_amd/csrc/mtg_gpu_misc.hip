@@ -18,6 +18,7 @@
 #include "mtg_find_het.h"
 #include "mtg_find_del.h"
 #include "mtg_find_snp.h"
+#include "mtg_find_msnp.h"
 
 namespace mtgi {
 
@@ -319,7 +320,7 @@ __global__ void __launch_bounds__(SCAN_TILE) k_scan(Index ix, const uint64_t* __
 
 /* The counter block of profile_run and of the find runs (FindStage): 64-bit slots zeroed by the run, named here for its kernels and for the
  * host's read-back alike.  Every block begins with k_profile's three; a total and a longest run are neighbours (k_profile_seq_scan writes
- * tot[0], k_profile_finish tot[1]).  The gap observers (homozygous insertions, deletions) share slots 4-8 and name their own from 10 up;
+ * tot[0], k_profile_finish tot[1]).  The gap observers (homozygous insertions, deletions, SNPs) share slots 4-8 and name their own from 10 up;
  * the heterozygous run names its slots where they differ */
 enum { CNT_POSITIONS, CNT_VALID, CNT_PRESENT, CNT_PROFILE };
 enum { CNT_RUNS = 4, CNT_RUNS_LONGEST, CNT_PROFILE_SLOTS = 8 };
@@ -327,6 +328,7 @@ enum { CNT_GAPS = 4, CNT_GAPS_LONGEST, CNT_GAP_CANDIDATES, CNT_GAP_CALLS, CNT_GA
 enum { CNT_HOMO_CLEAN = 10, CNT_HOMO_FUZZY, CNT_SMALL_CLEAN, CNT_SMALL_FUZZY };
 enum { CNT_DEL_CLEAN = 10, CNT_DEL_FUZZY, CNT_DEL_FALLBACK };
 enum { CNT_SNP_SOLO = 10 };
+enum { CNT_MSNP_FULL = 11, CNT_MSNP_PARTIAL, CNT_MSNP_LONG };
 enum { CNT_HET_LISTED = 4, CNT_HET_CALLS = 6, CNT_HET_CANDIDATES = 8, CNT_HET_RAW_SITES, CNT_HET_FILTERED, CNT_HET_SUPPRESSED, CNT_HET_CLEAN, CNT_HET_FUZZY, CNT_HET_SMALL };
 
 /* profile along packed sequences: the tile of k_scan (scan_tile_stage: the tile's m-mers hashed once in LDS, Bloom blocks staged by coalesced
@@ -770,6 +772,124 @@ struct SoloObserver {
     {
         st.n_positions = c[CNT_POSITIONS]; st.n_gaps = c[CNT_GAPS_SEEN]; st.n_candidates = n_cand; st.n_calls = c[CNT_SNP_SOLO];
     }
+};
+
+/* ---- `find` for close homozygous SNPs (include/mtg_fill.h: mtg_index_find_msnp_sequences; the rule: mtg_find_msnp.h).  The gaps are those of
+ * the other gap observers, marked and listed by the same kernels for MultiObserver; a gap makes several calls, so the middle is its own:
+ * k_msnp_bound: per candidate the room for its calls, L / m (0 for a gap that is not judged); k_profile_seq_scan turns it into the slab offsets.
+ * k_msnp_judge: one wave per candidate, the chain; its calls go to the gap's slab as non-zero entries, the rest of the slab stays 0.
+ * FindStage::calls_tail lists the non-zero entries of all slabs in order -- ascending gap, then pos -- and k_msnp_emit writes their records.
+ * k_msnp_gaps: the per-candidate records. */
+__global__ void __launch_bounds__(RUNS_BLOCK) k_msnp_bound(const mtg_run* __restrict__ gaps, const uint32_t* __restrict__ cand, uint64_t ncand, int m, uint32_t* bound)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    if (c < ncand) bound[c] = msnp_max_calls(gaps[cand[c]].length, m);
+}
+/* a word of the wave's text: lane `from` (uniform) holds it; a lane beyond the text holds 0 */
+__device__ __forceinline__ uint64_t msnp_lane_word(uint64_t tw, uint32_t from)
+{
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)tw, (int)from, 64), hi = (uint32_t)__shfl((int)(uint32_t)(tw >> 32), (int)from, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+/* the leading ones of one half of a ballot (windows 0 .. 31 of an alternative; a lane at or beyond cap votes 0) */
+__device__ __forceinline__ uint32_t msnp_leading(uint32_t half) { return (uint32_t)__builtin_ctzll((unsigned long long)(uint32_t)~half | (1ull << 32)); }
+/* The observer on one candidate gap, one wave each (four to a workgroup): a gap of L <= 254 positions from `start`, both k-mers anchors, so
+ * the text [start, start + L + k) lies in the sequence and holds nucleotides only.  Its at most MSNP_TEXT_WORDS packed words are the wave's
+ * private copy, word i in a register of lane i; no other word is read, and a call changes the copy, never the input.  A step at cursor c
+ * fetches the three words from (start % 32 + c) / 32 on by uniform lane reads; lane l takes window j = l % 32 (< cap) of the k-mer at
+ * start + c + j (Bloom filter, then the table): lanes 0-31 the first alternative in A, C, T, G order, lanes 32-63 the second, then lanes
+ * 0-31 the third -- all three counts are needed.  A count is the leading ones of its half of the ballot; winner and stop tests are
+ * msnp_winner / msnp_stop, uniform in the wave.  slab[slab_off[c] ..] receives the entries (msnp_entry), out[2c] = consumed,
+ * out[2c + 1] = calls.  CNT_MSNP_FULL / _PARTIAL / _LONG += 1 per gap taken whole / in part / not judged (L >= 255) */
+__global__ void __launch_bounds__(FIND_WAVES * 64) k_msnp_judge(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off, const mtg_run* __restrict__ gaps,
+                                                                const uint32_t* __restrict__ cand, uint64_t ncand, int m, const uint64_t* __restrict__ slab_off, uint32_t* slab,
+                                                                uint32_t* out, unsigned long long* counters)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t c = (uint64_t)blockIdx.x * FIND_WAVES + (threadIdx.x >> 6);
+    if (c >= ncand) return; /* (uniform in the wave; the kernel has no workgroup barrier) */
+    const mtg_run g = gaps[cand[c]];
+    const uint32_t L = g.length;
+    if (!msnp_is_judged(L)) {
+        if (lane == 0) { out[2 * c] = 0u; out[2 * c + 1] = 0u; atomicAdd(&counters[CNT_MSNP_LONG], 1ull); }
+        return;
+    }
+    const int k = ix.k;
+    const uint32_t nw = msnp_text_words(g.start, L, k), rel0 = g.start & 31u;
+    uint64_t tw = lane < nw ? words[word_off[g.seq] + (g.start >> 5) + lane] : 0ull;
+    uint32_t* entries = slab + slab_off[c];
+    const uint32_t half = lane >> 5, j = lane & 31u;
+    const uint64_t cmpl = 0xAAAAAAAAAAAAAAAAULL & kmask(k);
+    uint32_t lines = 0, at = 0, n = 0;
+    while (at != L) {
+        const uint32_t rel = rel0 + at, w0 = rel >> 5, r = rel & 31u, cap = msnp_cap(L, at, k);
+        const uint64_t t0 = msnp_lane_word(tw, w0), t1 = msnp_lane_word(tw, w0 + 1u), t2 = msnp_lane_word(tw, w0 + 2u);
+        const uint32_t ref = (uint32_t)(snp_text_kmer(t0, t1, t2, r, k) >> (2 * (k - 1))) & 3u;
+        const bool mine = j < cap;
+        const uint64_t km = mine ? snp_text_kmer(t0, t1, t2, r + j, k) : 0ull;
+        uint32_t f0 = 0, f1 = 0, f2 = 0;
+        for (uint32_t it = 0; it < 2u; it++) {
+            bool solid = false;
+            if (mine && 2u * it + half < 3u) {
+                Kmer x;
+                x.r = snp_window(km, (int)j, k, snp_alt(ref, 2u * it + half)) ^ cmpl;
+                x.f = revcomp(x.r, k);
+                solid = bloom_test(ix.bloom, x, k) && abundance(ix, x, lines) != 0;
+            }
+            const unsigned long long bal = __ballot(solid);
+            if (it == 0) { f0 = msnp_leading((uint32_t)bal); f1 = msnp_leading((uint32_t)(bal >> 32)); }
+            else f2 = msnp_leading((uint32_t)bal);
+        }
+        uint32_t best;
+        const uint32_t alt = snp_alt(ref, msnp_winner(f0, f1, f2, k, &best));
+        if (msnp_stop(at, best, L, m)) break;
+        if (lane == 0) entries[n] = msnp_entry(at, alt, ref);
+        n++;
+        const uint32_t gp = rel + (uint32_t)k - 1u;
+        if (lane == (gp >> 5)) tw = msnp_substituted(tw, gp, alt);
+        at += best;
+    }
+    if (lane == 0) {
+        out[2 * c] = at; out[2 * c + 1] = n;
+        if (at) atomicAdd(&counters[at == L ? CNT_MSNP_FULL : CNT_MSNP_PARTIAL], 1ull);
+    }
+}
+/* the gap of slab entry e: the last candidate whose slab begins at or before e (a candidate without room shares its offset with the next) */
+__device__ __forceinline__ uint64_t msnp_owner(const uint64_t* __restrict__ slab_off, uint64_t ncand, uint64_t e)
+{
+    uint64_t lo = 0, hi = ncand; /* slab_off[lo] <= e < slab_off[hi] */
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (slab_off[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+/* the records of the calls: call j is slab entry sel[j]; kind 6, left / right the gap's two k-mers for every SNP of the gap */
+__global__ void __launch_bounds__(RUNS_BLOCK) k_msnp_emit(const mtg_run* __restrict__ gaps, const uint32_t* __restrict__ cand, uint64_t ncand, const uint64_t* __restrict__ slab_off,
+                                                          const uint32_t* __restrict__ slab, const uint32_t* __restrict__ sel, uint64_t n, int k, mtg_find_call* calls)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t e = sel[j], o = slab[e];
+    const mtg_run g = gaps[cand[msnp_owner(slab_off, ncand, e)]];
+    mtg_find_call q;
+    q.seq = g.seq; q.pos = msnp_pos_of(g.start, o, k); q.kind = 6u; q.repeat = 0u; q.left = g.start - 1u; q.right = g.start + g.length; q.ins = snp_ins_of(o);
+    calls[j] = q;
+}
+__global__ void __launch_bounds__(RUNS_BLOCK) k_msnp_gaps(const mtg_run* __restrict__ gaps, const uint32_t* __restrict__ cand, const uint32_t* __restrict__ out, uint64_t n,
+                                                          mtg_find_msnp_gap* recs)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    if (c >= n) return;
+    const mtg_run g = gaps[cand[c]];
+    mtg_find_msnp_gap q;
+    q.seq = g.seq; q.start = g.start; q.length = g.length; q.consumed = out[2 * c]; q.n_snps = out[2 * c + 1];
+    recs[c] = q;
+}
+/* the candidate test for k_gap_mark, which hands its max_repeat argument through: the run passes snp_min_val there (max_repeat plays no part
+ * in this rule) */
+struct MultiObserver {
+    static MTG_DEV bool is_candidate(const mtg_run& g, int k, int snp_min_val) { return gap_is_msnp_candidate(g.length, g.flags, k, snp_min_val); }
 };
 
 /* ---- `find` for heterozygous insertions (include/mtg_fill.h: mtg_index_find_het_sequences; the rule and the word-level logic: mtg_find_het.h).
@@ -1443,6 +1563,82 @@ int find_snp_run(const mtg_index* idx, const uint64_t* words, size_t nwords, con
                  mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_snp_stats* st)
 {
     return find_gap_run<SoloObserver>(idx, words, nwords, word_off, len, nseq, bad, max_repeat, calls, cap, n_calls, device_ptrs, st);
+}
+
+/* `find` for close homozygous SNPs (mtg_index_find_msnp_sequences / _packed_device): the stage, the gaps and their candidates as in
+ * find_gap_run, then the slabs, the chain, and the calls listed from the slabs by calls_tail.  gap_recs (gap_cap records, may be null; host
+ * or device memory as calls) receives the first gap_cap per-candidate records, *n_gap_recs (may be null) their total */
+int find_msnp_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
+                  int snp_min_val, mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_msnp_gap* gap_recs, size_t gap_cap, size_t* n_gap_recs, int device_ptrs,
+                  mtg_find_msnp_stats* st)
+{
+    FindStage S;
+    if (n_gap_recs) *n_gap_recs = 0;
+    if (int rc = S.begin(idx, words, nwords, word_off, len, nseq, bad, nullptr, false, max_repeat, n_calls, st, device_ptrs); rc || nseq == 0) return rc;
+    const int k = S.k;
+    const SeqInput& in = S.in;
+    DevBuf d_gaps, d_mark, d_cand, d_bound, d_slab_off, d_slab, d_out, d_recs;
+    hipEvent_t e_gaps[2];
+    HIP_TRY(S.events.make(e_gaps[0])); HIP_TRY(S.events.make(e_gaps[1]));
+    uint64_t n_gaps_all = 0, n_cand = 0, total = 0;
+    /* 1. the planes, the gaps counted */
+    if (int rc = S.planes<false>([&] { hipLaunchKernelGGL(k_profile_count<true>, S.grid(), dim3(RUNS_BLOCK), 0, 0, S.d_v.as<uint64_t>(), S.d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, S.d_cnt.as<uint32_t>()); },
+                                 CNT_GAPS, "gaps", &n_gaps_all)) return rc;
+    if (n_gaps_all) {
+        /* 2. the gaps written, the candidates marked and listed in order */
+        HIP_TRY(d_mark.alloc((size_t)n_gaps_all * 4));
+        if (int rc = S.gaps(n_gaps_all, d_gaps, e_gaps[0])) return rc;
+        hipLaunchKernelGGL(k_gap_mark<MultiObserver>, dim3((unsigned)((n_gaps_all + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, k, snp_min_val, d_mark.as<uint32_t>(), S.cnt());
+        if (int rc = S.compact(d_mark.as<uint32_t>(), n_gaps_all, CNT_GAP_CANDIDATES, d_cand, ~0ull, &n_cand)) return rc;
+        HIP_TRY(hipEventRecord(e_gaps[1], 0));
+    }
+    if (n_cand) {
+        /* 3. a slab of L / m entries per candidate; the chain, one wave per candidate; the calls listed from the slabs and written */
+        const unsigned nb = (unsigned)((n_cand + RUNS_BLOCK - 1) / RUNS_BLOCK);
+        HIP_TRY(d_bound.alloc((size_t)n_cand * 4)); HIP_TRY(d_slab_off.alloc((size_t)n_cand * 8)); HIP_TRY(d_out.alloc((size_t)n_cand * 8));
+        HIP_TRY(hipEventRecord(S.e_tail[0], 0));
+        hipLaunchKernelGGL(k_msnp_bound, dim3(nb), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), n_cand, snp_min_val, d_bound.as<uint32_t>());
+        hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_bound.as<uint32_t>(), (size_t)n_cand, d_slab_off.as<uint64_t>(), S.cnt() + CNT_GAP_CALLS);
+        HIP_TRY(hipGetLastError());
+        unsigned long long n_slab = 0;
+        HIP_TRY(hipMemcpy(&n_slab, S.cnt() + CNT_GAP_CALLS, 8, hipMemcpyDeviceToHost));
+        if (n_slab > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 possible SNPs in the candidate gaps"); return MTG_ERR_ARG; }
+        HIP_TRY(d_slab.alloc((size_t)n_slab * 4));
+        if (n_slab) HIP_TRY(hipMemsetAsync(d_slab.p, 0, (size_t)n_slab * 4, 0));
+        hipLaunchKernelGGL(k_msnp_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, in.words, in.word_off, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(),
+                           n_cand, snp_min_val, d_slab_off.as<uint64_t>(), d_slab.as<uint32_t>(), d_out.as<uint32_t>(), S.cnt());
+        const uint64_t keep_recs = gap_recs ? std::min<uint64_t>(n_cand, gap_cap) : 0;
+        mtg_find_msnp_gap* pr = gap_recs;
+        if (keep_recs) {
+            if (!device_ptrs) { HIP_TRY(d_recs.alloc((size_t)keep_recs * sizeof(mtg_find_msnp_gap))); pr = d_recs.as<mtg_find_msnp_gap>(); }
+            hipLaunchKernelGGL(k_msnp_gaps, dim3((unsigned)((keep_recs + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), d_out.as<uint32_t>(), keep_recs, pr);
+        }
+        if (n_slab) {
+            if (int rc = S.calls_tail(d_slab.as<uint32_t>(), n_slab, CNT_GAP_CALLS, calls, cap, &total, [&](const uint32_t* sel, uint64_t keep, mtg_find_call* out) {
+                    hipLaunchKernelGGL(k_msnp_emit, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), n_cand, d_slab_off.as<uint64_t>(),
+                                       d_slab.as<uint32_t>(), sel, keep, k, out);
+                })) return rc;
+        } else {
+            HIP_TRY(hipEventRecord(S.e_tail[1], 0));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventSynchronize(S.e_tail[1]));
+            if (int rc = S.add_span(S.e_tail[0], S.e_tail[1])) return rc;
+        }
+        if (keep_recs && !device_ptrs) HIP_TRY(hipMemcpy(gap_recs, pr, (size_t)keep_recs * sizeof(mtg_find_msnp_gap), hipMemcpyDeviceToHost));
+    }
+    if (n_gaps_all) {
+        HIP_TRY(hipEventSynchronize(e_gaps[1]));
+        if (int rc = S.add_span(e_gaps[0], e_gaps[1])) return rc;
+    }
+    if (int rc = S.read_counters()) return rc;
+    *n_calls = (size_t)total;
+    if (n_gap_recs) *n_gap_recs = (size_t)n_cand;
+    if (st) {
+        st->n_positions = S.c[CNT_POSITIONS]; st->n_gaps = S.c[CNT_GAPS_SEEN]; st->n_candidates = n_cand; st->n_calls = total;
+        st->n_full = S.c[CNT_MSNP_FULL]; st->n_partial = S.c[CNT_MSNP_PARTIAL]; st->n_long = S.c[CNT_MSNP_LONG];
+        st->kernel_ms = (double)S.ms;
+    }
+    return MTG_OK;
 }
 
 /* `find` for heterozygous insertions over packed sequences (mtg_index_find_het_sequences / _packed_device).  device_ptrs = 0: words / word_off /

@@ -148,6 +148,12 @@ __attribute__((weak)) int find_snp_run(const mtg_index*, const uint64_t*, size_t
     set_error("this build has no device code for find");
     return MTG_ERR_NO_DEVICE;
 }
+__attribute__((weak)) int find_msnp_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, int, int, mtg_find_call*, size_t, size_t*,
+                                        mtg_find_msnp_gap*, size_t, size_t*, int, mtg_find_msnp_stats*)
+{
+    set_error("this build has no device code for find");
+    return MTG_ERR_NO_DEVICE;
+}
 __attribute__((weak)) int find_het_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, const uint64_t*, int, int, mtg_find_call*, size_t,
                                        size_t*, int, mtg_find_het_stats*)
 {
@@ -1938,7 +1944,7 @@ int mtg_index_profile_packed_device(const mtg_index* idx, const uint64_t* d_word
     return mtgi::profile_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, d_pos_off, 0, d_out, d_runs, runs_cap, n_runs, 1, st);
 }
 
-/* the argument checks of the eight find entries; have_input: the input arrays that nseq asks for are there */
+/* the argument checks of the ten find entries; have_input: the input arrays that nseq asks for are there */
 static int find_check_args(const mtg_index* idx, bool have_input, int max_repeat, const mtg_find_call* calls, size_t cap, const size_t* n_calls)
 {
     if (!idx || !n_calls || !have_input || (cap && !calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
@@ -1986,6 +1992,30 @@ int mtg_index_find_snp_packed_device(const mtg_index* idx, const uint64_t* d_wor
 {
     if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), max_repeat, d_calls, cap, n_calls)) return rc;
     return mtgi::find_snp_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, d_calls, cap, n_calls, 1, st);
+}
+
+/* what the two multi-SNP entries ask beyond find_check_args: 1 <= snp_min_val <= k, and an array where gap_cap asks for one */
+static int find_msnp_check_args(const mtg_index* idx, int snp_min_val, const mtg_find_msnp_gap* gaps, size_t gap_cap)
+{
+    if (gap_cap && !gaps) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    if (snp_min_val < 1 || snp_min_val > idx->dev.k) { mtgi::set_error("snp_min_val must be 1 .. k"); return MTG_ERR_ARG; }
+    return MTG_OK;
+}
+int mtg_index_find_msnp_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, int snp_min_val, mtg_find_call* calls, size_t cap, size_t* n_calls,
+                                  mtg_find_msnp_gap* gaps, size_t gap_cap, size_t* n_gaps, mtg_find_msnp_stats* st)
+{
+    if (int rc = find_check_args(idx, !nseq || seqs, max_repeat, calls, cap, n_calls)) return rc;
+    if (int rc = find_msnp_check_args(idx, snp_min_val, gaps, gap_cap)) return rc;
+    PackedSeqs P;
+    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, P)) return MTG_ERR_ARG;
+    return mtgi::find_msnp_run(idx, P.words.data(), P.words.size(), P.off.data(), P.len.data(), nseq, P.bad.data(), max_repeat, snp_min_val, calls, cap, n_calls, gaps, gap_cap, n_gaps, 0, st);
+}
+int mtg_index_find_msnp_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat, int snp_min_val,
+                                      mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_msnp_gap* d_gaps, size_t gap_cap, size_t* n_gaps, mtg_find_msnp_stats* st)
+{
+    if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), max_repeat, d_calls, cap, n_calls)) return rc;
+    if (int rc = find_msnp_check_args(idx, snp_min_val, d_gaps, gap_cap)) return rc;
+    return mtgi::find_msnp_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, snp_min_val, d_calls, cap, n_calls, d_gaps, gap_cap, n_gaps, 1, st);
 }
 
 int mtg_index_find_het_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, const uint8_t* const* repeated, int max_repeat, int branching_filter, mtg_find_call* calls,

@@ -597,6 +597,9 @@ int find_del_run(const mtg_index* idx, const uint64_t* words, size_t nwords, con
                  mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_del_stats* st);
 int find_snp_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
                  mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_snp_stats* st);
+int find_msnp_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
+                  int snp_min_val, mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_msnp_gap* gap_recs, size_t gap_cap, size_t* n_gap_recs, int device_ptrs,
+                  mtg_find_msnp_stats* st);
 int find_het_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, const uint64_t* rep,
                  int max_repeat, int branching_filter, mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_het_stats* st);
 int find_main(int argc, const char* const* argv);

@@ -117,9 +117,17 @@ class FindSnpStats(C.Structure):
                 ("reserved", C.c_uint64 * 3)]
 
 
+class FindMsnpStats(C.Structure):
+    _fields_ = [("n_positions", C.c_uint64), ("n_gaps", C.c_uint64), ("n_candidates", C.c_uint64), ("n_calls", C.c_uint64), ("kernel_ms", C.c_double),
+                ("n_full", C.c_uint64), ("n_partial", C.c_uint64), ("n_long", C.c_uint64)]
+
+
+# a candidate gap of the multi-SNP observer (mtg_find_msnp_gap): consumed = length: taken, 0 < consumed < length: in part, 0: untouched
+MSNP_GAP_DTYPE = np.dtype([("seq", np.uint32), ("start", np.uint32), ("length", np.uint32), ("consumed", np.uint32), ("n_snps", np.uint32)])
+
 # a call of `find` (mtg_find_call): kind 0 = homozygous insertion site, 1 = homozygous insertion of 1-2 nt, 2 = heterozygous site,
-# 3 = heterozygous insertion of 1-2 nt, 4 = homozygous deletion, 5 = isolated homozygous SNP; ins indexes FIND_INSERTIONS (kinds 1 and 3), is the
-# deleted length (kind 4) or holds ALT's ASCII code in bits 0-7 and REF's in bits 8-15 (kind 5)
+# 3 = heterozygous insertion of 1-2 nt, 4 = homozygous deletion, 5 = isolated homozygous SNP, 6 = SNP of a multi-SNP gap; ins indexes
+# FIND_INSERTIONS (kinds 1 and 3), is the deleted length (kind 4) or holds ALT's ASCII code in bits 0-7 and REF's in bits 8-15 (kinds 5 and 6)
 CALL_DTYPE = np.dtype([("seq", np.uint32), ("pos", np.uint32), ("kind", np.uint32), ("repeat", np.uint32), ("left", np.uint32), ("right", np.uint32), ("ins", np.uint32)])
 FIND_INSERTIONS = ("A", "C", "G", "T", "AA", "AC", "AG", "AT", "CA", "CC", "CG", "CT", "GA", "GC", "GG", "GT", "TA", "TC", "TG", "TT")
 
@@ -235,6 +243,10 @@ def _bind(lib):
     lib.mtg_index_find_del_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindDelStats)]
     lib.mtg_index_find_snp_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindSnpStats)]
     lib.mtg_index_find_snp_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindSnpStats)]
+    lib.mtg_index_find_msnp_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), C.c_void_p, C.c_size_t, P(C.c_size_t),
+                                                  P(FindMsnpStats)]
+    lib.mtg_index_find_msnp_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), C.c_void_p,
+                                                      C.c_size_t, P(C.c_size_t), P(FindMsnpStats)]
     lib.mtg_index_find_het_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindHetStats)]
     lib.mtg_index_find_het_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t),
                                                      P(FindHetStats)]
@@ -626,6 +638,36 @@ class Index:
         total, st = C.c_size_t(), FindSnpStats()
         _check(self.lib.mtg_index_find_snp_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap, C.byref(total), C.byref(st)))
         return total.value, {f[0]: getattr(st, f[0]) for f in FindSnpStats._fields_[:5]}
+
+    def find_msnp_sequences(self, seqs, max_repeat=5, snp_min_val=5, cap=None, gaps=True):
+        """`find` for close homozygous SNPs, the forward multi-SNP observer (kind 6: pos = the SNP's position, ins = ALT's ASCII code | REF's << 8,
+        left / right = the gap's two k-mers) of seqs against the graph; returns (calls as a CALL_DTYPE array in the order of the scan, the
+        candidate gaps as a MSNP_GAP_DTYPE array -- None with gaps=False, which passes NULL --, stats dict).  cap as in find_homo_sequences."""
+        n = len(seqs)
+        arr = (C.c_char_p * n)(*[s.encode() for s in seqs])
+        room = 1024 if cap is None else int(cap)
+        groom = 256 if gaps else 0
+        while True:
+            calls = np.zeros(room, dtype=CALL_DTYPE)
+            recs = np.zeros(groom, dtype=MSNP_GAP_DTYPE)
+            total, gtotal, st = C.c_size_t(), C.c_size_t(), FindMsnpStats()
+            _check(self.lib.mtg_index_find_msnp_sequences(self.h, arr, n, max_repeat, snp_min_val, calls.ctypes.data if room else None, room, C.byref(total),
+                                                          recs.ctypes.data if groom else None, groom, C.byref(gtotal) if gaps else None, C.byref(st)))
+            if (cap is not None or total.value <= room) and gtotal.value <= groom:
+                break
+            if cap is None:
+                room = max(room, total.value)
+            groom = max(groom, gtotal.value)
+        stats = {f[0]: getattr(st, f[0]) for f in FindMsnpStats._fields_}
+        return calls[:min(total.value, room)], (recs[:gtotal.value] if gaps else None), stats
+
+    def find_msnp_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, snp_min_val, calls_ptr, cap, gaps_ptr=None, gap_cap=0):
+        """the same on packed sequences in device memory (pointers as integers; calls_ptr: device array of cap mtg_find_call, gaps_ptr: device array
+        of gap_cap mtg_find_msnp_gap or None); returns (total calls, total candidate gaps, stats dict)"""
+        total, gtotal, st = C.c_size_t(), C.c_size_t(), FindMsnpStats()
+        _check(self.lib.mtg_index_find_msnp_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, snp_min_val, calls_ptr, cap, C.byref(total), gaps_ptr, gap_cap,
+                                                          C.byref(gtotal), C.byref(st)))
+        return total.value, gtotal.value, {f[0]: getattr(st, f[0]) for f in FindMsnpStats._fields_}
 
     def find_het_sequences(self, seqs, repeated=None, max_repeat=5, branching_filter=15, cap=None):
         """`find` for heterozygous insertions: the sites (kind 2) and the insertions of 1-2 nt (kind 3) of seqs against the graph; returns (calls
