@@ -499,21 +499,23 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_profile_finish(mtg_run* runs, ui
 }
 
 /* ---- `find` over the gaps of the scan (include/mtg_fill.h: mtg_index_find_homo_sequences, mtg_index_find_del_sequences).  The gaps come from
- * k_profile_count<true> / k_profile_write<true> as mtg_run records (flags: mtg_find_gaps.h).  An Observer (HomoObserver, DelObserver, SoloObserver below) is
- * one kind of call on a gap: its candidate test, its judge kernel, the record of a call and its statistics.
+ * k_profile_count<true> / k_profile_write<true> as mtg_run records (flags: mtg_find_gaps.h).  An Observer (HomoObserver, DelObserver, SoloObserver,
+ * MultiObserver below) is one kind of call on a gap: its candidate test and which argument of the run that test takes (candidate_param), the
+ * calls on the candidates (calls, run by find_gap_run) and its statistics.  An observer with at most one call per gap has a judge kernel and the
+ * record of a call, and takes the rest from OneCallPerGap.
  * k_gap_mark: one thread per gap, the observer's candidate test alone -- mark[i] = the gap is a candidate; CNT_GAPS_SEEN += gaps the observers see.
  * k_mark_count / k_profile_seq_scan / k_mark_index: the indices of the non-zero marks in ascending order (counts per workgroup, their
  * exclusive prefix sums, then every workgroup numbers its own); used for the candidates and, after the judge kernel, for the calls.
  * k_gap_emit: the records of the calls: call j is candidate sel[j] */
 template <typename Observer>
-__global__ void __launch_bounds__(RUNS_BLOCK) k_gap_mark(const mtg_run* __restrict__ gaps, uint64_t n, int k, int max_repeat, uint32_t* mark, unsigned long long* counters)
+__global__ void __launch_bounds__(RUNS_BLOCK) k_gap_mark(const mtg_run* __restrict__ gaps, uint64_t n, int k, int cand_param, uint32_t* mark, unsigned long long* counters)
 {
     const uint64_t i = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
     bool seen = false;
     if (i < n) {
         const mtg_run g = gaps[i];
         seen = (g.flags & 2u) != 0;
-        mark[i] = Observer::is_candidate(g, k, max_repeat) ? 1u : 0u;
+        mark[i] = Observer::is_candidate(g, k, cand_param) ? 1u : 0u;
     }
     const unsigned long long bal = __ballot(seen);
     if ((threadIdx.x & 63u) == 0 && bal) atomicAdd(&counters[CNT_GAPS_SEEN], (unsigned long long)__popcll(bal));
@@ -623,8 +625,16 @@ __global__ void __launch_bounds__(FIND_WAVES * 64) k_find_assemble(Index ix, con
         if (out) atomicAdd(&counters[((out >> 1) & 1u) ? (r ? CNT_SMALL_FUZZY : CNT_SMALL_CLEAN) : (r ? CNT_HOMO_FUZZY : CNT_HOMO_CLEAN)], 1ull);
     }
 }
+/* What the observers with at most one call per gap share: their candidate test takes max_repeat, and their calls are Observer::judge, one wave
+ * per candidate, then k_gap_emit<Observer> (the body stands with the stage of the find runs, further down) */
+namespace { struct FindStage; }
+template <typename Observer> struct OneCallPerGap {
+    static int candidate_param(int max_repeat, int) { return max_repeat; }
+    static int calls(FindStage& S, const FindArgs& a, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand, uint64_t* total);
+};
+
 /* the gap observer of the homozygous insertions: gap_is_candidate (mtg_find_gaps.h), k_find_assemble, kinds 0 (site) and 1 (1-2 nt) */
-struct HomoObserver {
+struct HomoObserver : OneCallPerGap<HomoObserver> {
     using Stats = mtg_find_stats;
     static MTG_DEV bool is_candidate(const mtg_run& g, int k, int max_repeat) { return gap_is_candidate(g.length, g.flags, k, max_repeat); }
     static void judge(const Index& ix, const uint64_t* words, const uint64_t* word_off, const uint32_t* len, const uint64_t* bad, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand,
@@ -689,7 +699,7 @@ __global__ void __launch_bounds__(FIND_WAVES * 64) k_del_judge(Index ix, const u
     }
 }
 /* the gap observer of the homozygous deletions: gap_is_del_candidate (mtg_find_del.h), k_del_judge, kind 4 */
-struct DelObserver {
+struct DelObserver : OneCallPerGap<DelObserver> {
     using Stats = mtg_find_del_stats;
     static MTG_DEV bool is_candidate(const mtg_run& g, int k, int max_repeat) { return gap_is_del_candidate(g.length, g.flags, k, max_repeat); }
     static void judge(const Index& ix, const uint64_t* words, const uint64_t* word_off, const uint32_t*, const uint64_t*, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand,
@@ -754,7 +764,7 @@ __global__ void __launch_bounds__(FIND_WAVES * 64) k_snp_judge(Index ix, const u
     }
 }
 /* the gap observer of the isolated homozygous SNPs: gap_is_snp_candidate (mtg_find_snp.h), k_snp_judge, kind 5 */
-struct SoloObserver {
+struct SoloObserver : OneCallPerGap<SoloObserver> {
     using Stats = mtg_find_snp_stats;
     static MTG_DEV bool is_candidate(const mtg_run& g, int k, int max_repeat) { return gap_is_snp_candidate(g.length, g.flags, k, max_repeat); }
     static void judge(const Index& ix, const uint64_t* words, const uint64_t* word_off, const uint32_t*, const uint64_t*, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand,
@@ -886,10 +896,18 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_msnp_gaps(const mtg_run* __restr
     q.seq = g.seq; q.start = g.start; q.length = g.length; q.consumed = out[2 * c]; q.n_snps = out[2 * c + 1];
     recs[c] = q;
 }
-/* the candidate test for k_gap_mark, which hands its max_repeat argument through: the run passes snp_min_val there (max_repeat plays no part
- * in this rule) */
+/* the gap observer of the close homozygous SNPs: gap_is_msnp_candidate (mtg_find_msnp.h) on snp_min_val, the slab middle (calls, with the
+ * stage of the find runs further down), kind 6 */
 struct MultiObserver {
+    using Stats = mtg_find_msnp_stats;
+    static int candidate_param(int, int snp_min_val) { return snp_min_val; }
     static MTG_DEV bool is_candidate(const mtg_run& g, int k, int snp_min_val) { return gap_is_msnp_candidate(g.length, g.flags, k, snp_min_val); }
+    static int calls(FindStage& S, const FindArgs& a, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand, uint64_t* total);
+    static void fill(Stats& st, const unsigned long long* c, uint64_t n_cand, uint64_t total)
+    {
+        st.n_positions = c[CNT_POSITIONS]; st.n_gaps = c[CNT_GAPS_SEEN]; st.n_candidates = n_cand; st.n_calls = total;
+        st.n_full = c[CNT_MSNP_FULL]; st.n_partial = c[CNT_MSNP_PARTIAL]; st.n_long = c[CNT_MSNP_LONG];
+    }
 };
 
 /* ---- `find` for heterozygous insertions (include/mtg_fill.h: mtg_index_find_het_sequences; the rule and the word-level logic: mtg_find_het.h).
@@ -1242,7 +1260,7 @@ int nw_run(const mtg_index* idx, const std::vector<NwPair>& pairs, std::vector<u
 }
 
 namespace {
-/* The packed sequences of scan_run / profile_run / find_homo_run / find_het_run as their kernels read them: words, word_off and len, and where
+/* The packed sequences of scan_run / profile_run / find_run as their kernels read them: words, word_off and len, and where
  * the run has them the bad plane, the rep plane (both of nwords words) and pos_off (one per sequence).  upload: the caller's arrays are host
  * memory and go to buffers of our own; take: they are device memory and are used as they are */
 struct SeqInput {
@@ -1314,21 +1332,19 @@ struct FindStage {
     int read_counters() { HIP_TRY(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost)); return MTG_OK; }
 
     /* The checks, *n_calls and the statistics zeroed; then, unless there is no sequence (the caller returns), the input taken or uploaded, the
-     * planes and counts allocated, the counters zeroed.  device_ptrs = 0: words / word_off / len / bad / rep are host arrays (nwords words
-     * each), 1: device memory (nwords unused) */
-    template <typename Stats>
-    int begin(const mtg_index* index, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t n, const uint64_t* bad, const uint64_t* rep, bool het,
-              int max_rep, size_t* n_calls, Stats* st, int dev_ptrs)
+     * planes and counts allocated, the counters zeroed.  The arrays of a: FindArgs (mtg_internal.h) */
+    template <typename Stats> int begin(const mtg_index* index, const FindArgs& a, bool het, Stats* st)
     {
         if (int rc = use_device_of(index)) return rc;
         if (!index || !index->dev.bloom.bits) { set_error("the index has no Bloom filter (MTG_BLOOM_BITS=0)"); return MTG_ERR_ARG; }
-        *n_calls = 0;
+        *a.n_calls = 0;
         if (st) *st = Stats{};
-        if (n == 0) return MTG_OK;
-        idx = index; nseq = n; k = idx->dev.k; device_ptrs = dev_ptrs;
-        max_repeat = max_rep > k - 2 ? k - 2 : max_rep;
-        if (device_ptrs) in.take(words, word_off, len, nseq, bad, rep);
-        else if (int rc = in.upload(words, nwords, word_off, len, nseq, bad, rep)) return rc;
+        if (a.nseq == 0) return MTG_OK;
+        idx = index; nseq = a.nseq; k = idx->dev.k; device_ptrs = a.device_ptrs;
+        max_repeat = a.max_repeat > k - 2 ? k - 2 : a.max_repeat;
+        if (device_ptrs) in.take(a.words, a.word_off, a.len, nseq, a.bad, a.rep);
+        else if (int rc = in.upload(a.words, a.nwords, a.word_off, a.len, nseq, a.bad, a.rep)) return rc;
+        size_t nwords = 0;
         if (int rc = in.plane_words(&nwords)) return rc;
         HIP_TRY(d_v.alloc(nwords * 8)); HIP_TRY(d_p.alloc(nwords * 8));
         if (het) { HIP_TRY(d_in2.alloc(nwords * 8)); HIP_TRY(d_out2.alloc(nwords * 8)); HIP_TRY(d_br.alloc(nwords * 8)); }
@@ -1385,7 +1401,7 @@ struct FindStage {
     }
     /* What every run ends with, the caller having recorded e_tail[0] ahead of its judging: the non-zero entries of mark[0 : n] are the calls,
      * counted into slot `slot`; emit(sel, keep, out) launches the kernel that writes the first keep = min(*total, cap) records, call j from
-     * entry sel[j], into device memory; they reach `calls` (the caller's device array, or host memory by one copy).  Ends the span and waits for it */
+     * entry sel[j], into device memory; they reach `calls` (the caller's device array, or host memory by one copy).  Ends the span (end_tail) */
     template <typename Emit> int calls_tail(const uint32_t* mark, uint64_t n, int slot, mtg_find_call* calls, size_t cap, uint64_t* total, Emit emit)
     {
         if (int rc = compact(mark, n, slot, d_sel, cap, total)) return rc;
@@ -1395,10 +1411,16 @@ struct FindStage {
             if (!device_ptrs) { HIP_TRY(d_calls.alloc((size_t)keep * sizeof(mtg_find_call))); pc = d_calls.as<mtg_find_call>(); }
             emit(d_sel.as<uint32_t>(), keep, pc);
         }
+        if (int rc = end_tail()) return rc;
+        if (keep && !device_ptrs) HIP_TRY(hipMemcpy(calls, pc, (size_t)keep * sizeof(mtg_find_call), hipMemcpyDeviceToHost));
+        return MTG_OK;
+    }
+    /* the end of the span that the caller began at e_tail[0], waited for: calls_tail's, and by itself the tail of a run that has nothing to list */
+    int end_tail()
+    {
         HIP_TRY(hipEventRecord(e_tail[1], 0));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventSynchronize(e_tail[1]));
-        if (keep && !device_ptrs) HIP_TRY(hipMemcpy(calls, pc, (size_t)keep * sizeof(mtg_find_call), hipMemcpyDeviceToHost));
         return add_span(e_tail[0], e_tail[1]);
     }
 };
@@ -1501,156 +1523,104 @@ int profile_run(const mtg_index* idx, const uint64_t* words, size_t nwords, cons
     return MTG_OK;
 }
 
-/* `find` by a gap observer over packed sequences.  device_ptrs = 0: words / word_off / len / bad are host arrays and calls host memory; 1: all
- * of them device memory (nwords unused, bad null) */
+/* The calls of the observers that make at most one call per gap (HomoObserver, DelObserver, SoloObserver): a result word per candidate, the
+ * observer's judge kernel, one wave per candidate, and the calls -- the non-zero results -- listed in order and written by k_gap_emit */
 template <typename Observer>
-static int find_gap_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
-                        mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, typename Observer::Stats* st)
+int OneCallPerGap<Observer>::calls(FindStage& S, const FindArgs& a, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand, uint64_t* total)
+{
+    const SeqInput& in = S.in;
+    DevBuf d_res;
+    HIP_TRY(d_res.alloc((size_t)n_cand * 4));
+    HIP_TRY(hipEventRecord(S.e_tail[0], 0));
+    Observer::judge(S.idx->dev, in.words, in.word_off, in.len, in.bad, gaps, cand, n_cand, S.max_repeat, d_res.as<uint32_t>(), S.cnt());
+    return S.calls_tail(d_res.as<uint32_t>(), n_cand, CNT_GAP_CALLS, a.calls, a.cap, total, [&](const uint32_t* sel, uint64_t keep, mtg_find_call* out) {
+        hipLaunchKernelGGL(k_gap_emit<Observer>, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, gaps, cand, d_res.as<uint32_t>(), sel, keep, S.k, out);
+    });
+}
+
+/* The multi-SNP observer's calls, several per gap: a slab of L / m entries per candidate; the chain, one wave per candidate; the per-candidate
+ * records (the first a.gap_cap of them, where a.gap_recs is given); the calls listed from the slabs and written.  Without a slab -- every
+ * candidate unjudged -- there is nothing to list, and the span ends by end_tail */
+int MultiObserver::calls(FindStage& S, const FindArgs& a, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand, uint64_t* total)
+{
+    const SeqInput& in = S.in;
+    DevBuf d_bound, d_slab_off, d_slab, d_out, d_recs;
+    const unsigned nb = (unsigned)((n_cand + RUNS_BLOCK - 1) / RUNS_BLOCK);
+    HIP_TRY(d_bound.alloc((size_t)n_cand * 4)); HIP_TRY(d_slab_off.alloc((size_t)n_cand * 8)); HIP_TRY(d_out.alloc((size_t)n_cand * 8));
+    HIP_TRY(hipEventRecord(S.e_tail[0], 0));
+    hipLaunchKernelGGL(k_msnp_bound, dim3(nb), dim3(RUNS_BLOCK), 0, 0, gaps, cand, n_cand, a.snp_min_val, d_bound.as<uint32_t>());
+    hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_bound.as<uint32_t>(), (size_t)n_cand, d_slab_off.as<uint64_t>(), S.cnt() + CNT_GAP_CALLS);
+    HIP_TRY(hipGetLastError());
+    unsigned long long n_slab = 0;
+    HIP_TRY(hipMemcpy(&n_slab, S.cnt() + CNT_GAP_CALLS, 8, hipMemcpyDeviceToHost));
+    if (n_slab > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 possible SNPs in the candidate gaps"); return MTG_ERR_ARG; }
+    HIP_TRY(d_slab.alloc((size_t)n_slab * 4));
+    if (n_slab) HIP_TRY(hipMemsetAsync(d_slab.p, 0, (size_t)n_slab * 4, 0));
+    hipLaunchKernelGGL(k_msnp_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, S.idx->dev, in.words, in.word_off, gaps, cand, n_cand, a.snp_min_val,
+                       d_slab_off.as<uint64_t>(), d_slab.as<uint32_t>(), d_out.as<uint32_t>(), S.cnt());
+    const uint64_t keep_recs = a.gap_recs ? std::min<uint64_t>(n_cand, a.gap_cap) : 0;
+    mtg_find_msnp_gap* pr = a.gap_recs;
+    if (keep_recs) {
+        if (!a.device_ptrs) { HIP_TRY(d_recs.alloc((size_t)keep_recs * sizeof(mtg_find_msnp_gap))); pr = d_recs.as<mtg_find_msnp_gap>(); }
+        hipLaunchKernelGGL(k_msnp_gaps, dim3((unsigned)((keep_recs + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, gaps, cand, d_out.as<uint32_t>(), keep_recs, pr);
+    }
+    if (n_slab) {
+        if (int rc = S.calls_tail(d_slab.as<uint32_t>(), n_slab, CNT_GAP_CALLS, a.calls, a.cap, total, [&](const uint32_t* sel, uint64_t keep, mtg_find_call* out) {
+                hipLaunchKernelGGL(k_msnp_emit, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, gaps, cand, n_cand, d_slab_off.as<uint64_t>(), d_slab.as<uint32_t>(), sel, keep,
+                                   S.k, out);
+            })) return rc;
+    } else if (int rc = S.end_tail()) return rc;
+    if (keep_recs && !a.device_ptrs) HIP_TRY(hipMemcpy(a.gap_recs, pr, (size_t)keep_recs * sizeof(mtg_find_msnp_gap), hipMemcpyDeviceToHost));
+    return MTG_OK;
+}
+
+/* `find` by a gap observer over packed sequences: what all of them share.  Between "there are candidates" and "the calls are written" the
+ * observer is on its own (Observer::calls) */
+template <typename Observer>
+static int find_gap_run(const mtg_index* idx, const FindArgs& a, typename Observer::Stats* st)
 {
     FindStage S;
-    if (int rc = S.begin(idx, words, nwords, word_off, len, nseq, bad, nullptr, false, max_repeat, n_calls, st, device_ptrs); rc || nseq == 0) return rc;
+    if (a.n_gap_recs) *a.n_gap_recs = 0;
+    if (int rc = S.begin(idx, a, false, st); rc || a.nseq == 0) return rc;
     const int k = S.k;
     const SeqInput& in = S.in;
-    DevBuf d_gaps, d_mark, d_cand, d_res;
+    DevBuf d_gaps, d_mark, d_cand;
     hipEvent_t e_gaps[2];
     HIP_TRY(S.events.make(e_gaps[0])); HIP_TRY(S.events.make(e_gaps[1]));
     uint64_t n_gaps_all = 0, n_cand = 0, total = 0;
     /* 1. the planes, the gaps counted */
-    if (int rc = S.planes<false>([&] { hipLaunchKernelGGL(k_profile_count<true>, S.grid(), dim3(RUNS_BLOCK), 0, 0, S.d_v.as<uint64_t>(), S.d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, S.d_cnt.as<uint32_t>()); },
+    if (int rc = S.planes<false>([&] { hipLaunchKernelGGL(k_profile_count<true>, S.grid(), dim3(RUNS_BLOCK), 0, 0, S.d_v.as<uint64_t>(), S.d_p.as<uint64_t>(), in.word_off, in.len, S.nseq, k, S.d_cnt.as<uint32_t>()); },
                                  CNT_GAPS, "gaps", &n_gaps_all)) return rc;
     if (n_gaps_all) {
         /* 2. the gaps written, the candidates marked and listed in order */
         HIP_TRY(d_mark.alloc((size_t)n_gaps_all * 4));
         if (int rc = S.gaps(n_gaps_all, d_gaps, e_gaps[0])) return rc;
-        hipLaunchKernelGGL(k_gap_mark<Observer>, dim3((unsigned)((n_gaps_all + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, k, S.max_repeat, d_mark.as<uint32_t>(), S.cnt());
+        hipLaunchKernelGGL(k_gap_mark<Observer>, dim3((unsigned)((n_gaps_all + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, k,
+                           Observer::candidate_param(S.max_repeat, a.snp_min_val), d_mark.as<uint32_t>(), S.cnt());
         if (int rc = S.compact(d_mark.as<uint32_t>(), n_gaps_all, CNT_GAP_CANDIDATES, d_cand, ~0ull, &n_cand)) return rc;
         HIP_TRY(hipEventRecord(e_gaps[1], 0));
     }
-    if (n_cand) {
-        /* 3. the observer, one wave per candidate; the calls listed in order and written */
-        HIP_TRY(d_res.alloc((size_t)n_cand * 4));
-        HIP_TRY(hipEventRecord(S.e_tail[0], 0));
-        Observer::judge(idx->dev, in.words, in.word_off, in.len, in.bad, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), n_cand, S.max_repeat, d_res.as<uint32_t>(), S.cnt());
-        if (int rc = S.calls_tail(d_res.as<uint32_t>(), n_cand, CNT_GAP_CALLS, calls, cap, &total, [&](const uint32_t* sel, uint64_t keep, mtg_find_call* out) {
-                hipLaunchKernelGGL(k_gap_emit<Observer>, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), d_res.as<uint32_t>(), sel, keep, k, out);
-            })) return rc;
-    }
+    /* 3. the observer on the candidates: the calls listed in order and written */
+    if (n_cand) { if (int rc = Observer::calls(S, a, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), n_cand, &total)) return rc; }
     if (n_gaps_all) {
         HIP_TRY(hipEventSynchronize(e_gaps[1]));
         if (int rc = S.add_span(e_gaps[0], e_gaps[1])) return rc;
     }
     if (int rc = S.read_counters()) return rc;
-    *n_calls = (size_t)total;
+    *a.n_calls = (size_t)total;
+    if (a.n_gap_recs) *a.n_gap_recs = (size_t)n_cand;
     if (st) { Observer::fill(*st, S.c, n_cand, total); st->kernel_ms = (double)S.ms; }
     return MTG_OK;
 }
 
-/* `find` for homozygous insertions (mtg_index_find_homo_sequences / _packed_device) and for homozygous deletions (mtg_index_find_del_sequences /
- * _packed_device): the gap run with their observers */
-int find_homo_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
-                  mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_stats* st)
-{
-    return find_gap_run<HomoObserver>(idx, words, nwords, word_off, len, nseq, bad, max_repeat, calls, cap, n_calls, device_ptrs, st);
-}
-int find_del_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
-                 mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_del_stats* st)
-{
-    return find_gap_run<DelObserver>(idx, words, nwords, word_off, len, nseq, bad, max_repeat, calls, cap, n_calls, device_ptrs, st);
-}
-
-/* `find` for isolated homozygous SNPs (mtg_index_find_snp_sequences / _packed_device): the gap run with SoloObserver */
-int find_snp_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
-                 mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_snp_stats* st)
-{
-    return find_gap_run<SoloObserver>(idx, words, nwords, word_off, len, nseq, bad, max_repeat, calls, cap, n_calls, device_ptrs, st);
-}
-
-/* `find` for close homozygous SNPs (mtg_index_find_msnp_sequences / _packed_device): the stage, the gaps and their candidates as in
- * find_gap_run, then the slabs, the chain, and the calls listed from the slabs by calls_tail.  gap_recs (gap_cap records, may be null; host
- * or device memory as calls) receives the first gap_cap per-candidate records, *n_gap_recs (may be null) their total */
-int find_msnp_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
-                  int snp_min_val, mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_msnp_gap* gap_recs, size_t gap_cap, size_t* n_gap_recs, int device_ptrs,
-                  mtg_find_msnp_stats* st)
+/* `find` for heterozygous insertions over packed sequences (mtg_index_find_het_sequences / _packed_device): no gaps, a run of its own on the
+ * stage.  Beyond the input: six planes of a bit per position and one HetEntry per candidate */
+static int find_het_run(const mtg_index* idx, const FindArgs& a, mtg_find_het_stats* st)
 {
     FindStage S;
-    if (n_gap_recs) *n_gap_recs = 0;
-    if (int rc = S.begin(idx, words, nwords, word_off, len, nseq, bad, nullptr, false, max_repeat, n_calls, st, device_ptrs); rc || nseq == 0) return rc;
-    const int k = S.k;
-    const SeqInput& in = S.in;
-    DevBuf d_gaps, d_mark, d_cand, d_bound, d_slab_off, d_slab, d_out, d_recs;
-    hipEvent_t e_gaps[2];
-    HIP_TRY(S.events.make(e_gaps[0])); HIP_TRY(S.events.make(e_gaps[1]));
-    uint64_t n_gaps_all = 0, n_cand = 0, total = 0;
-    /* 1. the planes, the gaps counted */
-    if (int rc = S.planes<false>([&] { hipLaunchKernelGGL(k_profile_count<true>, S.grid(), dim3(RUNS_BLOCK), 0, 0, S.d_v.as<uint64_t>(), S.d_p.as<uint64_t>(), in.word_off, in.len, nseq, k, S.d_cnt.as<uint32_t>()); },
-                                 CNT_GAPS, "gaps", &n_gaps_all)) return rc;
-    if (n_gaps_all) {
-        /* 2. the gaps written, the candidates marked and listed in order */
-        HIP_TRY(d_mark.alloc((size_t)n_gaps_all * 4));
-        if (int rc = S.gaps(n_gaps_all, d_gaps, e_gaps[0])) return rc;
-        hipLaunchKernelGGL(k_gap_mark<MultiObserver>, dim3((unsigned)((n_gaps_all + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), n_gaps_all, k, snp_min_val, d_mark.as<uint32_t>(), S.cnt());
-        if (int rc = S.compact(d_mark.as<uint32_t>(), n_gaps_all, CNT_GAP_CANDIDATES, d_cand, ~0ull, &n_cand)) return rc;
-        HIP_TRY(hipEventRecord(e_gaps[1], 0));
-    }
-    if (n_cand) {
-        /* 3. a slab of L / m entries per candidate; the chain, one wave per candidate; the calls listed from the slabs and written */
-        const unsigned nb = (unsigned)((n_cand + RUNS_BLOCK - 1) / RUNS_BLOCK);
-        HIP_TRY(d_bound.alloc((size_t)n_cand * 4)); HIP_TRY(d_slab_off.alloc((size_t)n_cand * 8)); HIP_TRY(d_out.alloc((size_t)n_cand * 8));
-        HIP_TRY(hipEventRecord(S.e_tail[0], 0));
-        hipLaunchKernelGGL(k_msnp_bound, dim3(nb), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), n_cand, snp_min_val, d_bound.as<uint32_t>());
-        hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_bound.as<uint32_t>(), (size_t)n_cand, d_slab_off.as<uint64_t>(), S.cnt() + CNT_GAP_CALLS);
-        HIP_TRY(hipGetLastError());
-        unsigned long long n_slab = 0;
-        HIP_TRY(hipMemcpy(&n_slab, S.cnt() + CNT_GAP_CALLS, 8, hipMemcpyDeviceToHost));
-        if (n_slab > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 possible SNPs in the candidate gaps"); return MTG_ERR_ARG; }
-        HIP_TRY(d_slab.alloc((size_t)n_slab * 4));
-        if (n_slab) HIP_TRY(hipMemsetAsync(d_slab.p, 0, (size_t)n_slab * 4, 0));
-        hipLaunchKernelGGL(k_msnp_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, in.words, in.word_off, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(),
-                           n_cand, snp_min_val, d_slab_off.as<uint64_t>(), d_slab.as<uint32_t>(), d_out.as<uint32_t>(), S.cnt());
-        const uint64_t keep_recs = gap_recs ? std::min<uint64_t>(n_cand, gap_cap) : 0;
-        mtg_find_msnp_gap* pr = gap_recs;
-        if (keep_recs) {
-            if (!device_ptrs) { HIP_TRY(d_recs.alloc((size_t)keep_recs * sizeof(mtg_find_msnp_gap))); pr = d_recs.as<mtg_find_msnp_gap>(); }
-            hipLaunchKernelGGL(k_msnp_gaps, dim3((unsigned)((keep_recs + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), d_out.as<uint32_t>(), keep_recs, pr);
-        }
-        if (n_slab) {
-            if (int rc = S.calls_tail(d_slab.as<uint32_t>(), n_slab, CNT_GAP_CALLS, calls, cap, &total, [&](const uint32_t* sel, uint64_t keep, mtg_find_call* out) {
-                    hipLaunchKernelGGL(k_msnp_emit, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_gaps.as<mtg_run>(), d_cand.as<uint32_t>(), n_cand, d_slab_off.as<uint64_t>(),
-                                       d_slab.as<uint32_t>(), sel, keep, k, out);
-                })) return rc;
-        } else {
-            HIP_TRY(hipEventRecord(S.e_tail[1], 0));
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventSynchronize(S.e_tail[1]));
-            if (int rc = S.add_span(S.e_tail[0], S.e_tail[1])) return rc;
-        }
-        if (keep_recs && !device_ptrs) HIP_TRY(hipMemcpy(gap_recs, pr, (size_t)keep_recs * sizeof(mtg_find_msnp_gap), hipMemcpyDeviceToHost));
-    }
-    if (n_gaps_all) {
-        HIP_TRY(hipEventSynchronize(e_gaps[1]));
-        if (int rc = S.add_span(e_gaps[0], e_gaps[1])) return rc;
-    }
-    if (int rc = S.read_counters()) return rc;
-    *n_calls = (size_t)total;
-    if (n_gap_recs) *n_gap_recs = (size_t)n_cand;
-    if (st) {
-        st->n_positions = S.c[CNT_POSITIONS]; st->n_gaps = S.c[CNT_GAPS_SEEN]; st->n_candidates = n_cand; st->n_calls = total;
-        st->n_full = S.c[CNT_MSNP_FULL]; st->n_partial = S.c[CNT_MSNP_PARTIAL]; st->n_long = S.c[CNT_MSNP_LONG];
-        st->kernel_ms = (double)S.ms;
-    }
-    return MTG_OK;
-}
-
-/* `find` for heterozygous insertions over packed sequences (mtg_index_find_het_sequences / _packed_device).  device_ptrs = 0: words / word_off /
- * len / bad / rep are host arrays (bad and rep of nwords words each, rep may be null) and calls host memory; 1: all of them device memory
- * (nwords unused, bad null).  Beyond the input: six planes of a bit per position and one HetEntry per candidate */
-int find_het_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, const uint64_t* rep,
-                 int max_repeat, int branching_filter, mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_het_stats* st)
-{
-    FindStage S;
-    if (int rc = S.begin(idx, words, nwords, word_off, len, nseq, bad, rep, true, max_repeat, n_calls, st, device_ptrs); rc || nseq == 0) return rc;
-    const int k = S.k;
-    max_repeat = S.max_repeat;
+    if (int rc = S.begin(idx, a, true, st); rc || a.nseq == 0) return rc;
+    const int k = S.k, max_repeat = S.max_repeat;
+    const size_t nseq = S.nseq;
     const SeqInput& in = S.in;
     DevBuf d_e, d_mark;
     const dim3 grid = S.grid();
@@ -1669,15 +1639,15 @@ int find_het_run(const mtg_index* idx, const uint64_t* words, size_t nwords, con
         HIP_TRY(hipEventRecord(S.e_tail[0], 0));
         hipLaunchKernelGGL(k_het_list, grid, dim3(RUNS_BLOCK), 0, 0, d_v, d_in2, d_out2, in.rep, in.word_off, in.len, nseq, k, max_repeat, S.d_before.as<uint64_t>(), d_e.as<HetEntry>(), n_cand);
         hipLaunchKernelGGL(k_het_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, idx->dev, in.words, in.word_off, in.len, in.bad, d_v, d_out2, d_br, in.rep,
-                           d_e.as<HetEntry>(), n_cand, max_repeat, branching_filter, cnt);
+                           d_e.as<HetEntry>(), n_cand, max_repeat, a.branching_filter, cnt);
         hipLaunchKernelGGL(k_het_chain, dim3(cb), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), n_cand, d_v, in.word_off, max_repeat);
         hipLaunchKernelGGL(k_het_final, dim3(cb), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), n_cand, d_v, in.word_off, max_repeat, d_mark.as<uint32_t>(), cnt);
-        if (int rc = S.calls_tail(d_mark.as<uint32_t>(), n_cand, CNT_HET_CALLS, calls, cap, &total, [&](const uint32_t* sel, uint64_t keep, mtg_find_call* out) {
+        if (int rc = S.calls_tail(d_mark.as<uint32_t>(), n_cand, CNT_HET_CALLS, a.calls, a.cap, &total, [&](const uint32_t* sel, uint64_t keep, mtg_find_call* out) {
                 hipLaunchKernelGGL(k_het_emit, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, d_e.as<HetEntry>(), sel, keep, out);
             })) return rc;
         if (int rc = S.read_counters()) return rc;
     }
-    *n_calls = (size_t)total;
+    *a.n_calls = (size_t)total;
     if (st) {
         const unsigned long long* c = S.c;
         st->n_positions = c[CNT_POSITIONS]; st->n_candidates = c[CNT_HET_CANDIDATES]; st->n_raw_sites = c[CNT_HET_RAW_SITES]; st->n_filtered = c[CNT_HET_FILTERED]; st->n_suppressed = c[CNT_HET_SUPPRESSED];
@@ -1685,6 +1655,26 @@ int find_het_run(const mtg_index* idx, const uint64_t* words, size_t nwords, con
         st->kernel_ms = (double)S.ms;
     }
     return MTG_OK;
+}
+
+/* The one run entry behind the ten find entries of the ABI; the only place where the statistics pointer gets its type back: the layer's run
+ * says which */
+template <typename Stats>
+static int find_run_as(int (*run)(const mtg_index*, const FindArgs&, Stats*), const mtg_index* idx, const FindArgs& a, void* stats)
+{
+    return run(idx, a, static_cast<Stats*>(stats));
+}
+int find_run(const mtg_index* idx, FindLayer layer, const FindArgs& args, void* stats)
+{
+    switch (layer) {
+        case FIND_HOMO: return find_run_as(find_gap_run<HomoObserver>, idx, args, stats);
+        case FIND_DEL: return find_run_as(find_gap_run<DelObserver>, idx, args, stats);
+        case FIND_SNP: return find_run_as(find_gap_run<SoloObserver>, idx, args, stats);
+        case FIND_MSNP: return find_run_as(find_gap_run<MultiObserver>, idx, args, stats);
+        case FIND_HET: return find_run_as(find_het_run, idx, args, stats);
+    }
+    set_error("invalid argument");
+    return MTG_ERR_ARG;
 }
 
 int bench_random_lines(uint64_t table_bytes, uint64_t n_chains, uint32_t chain_len, uint32_t line_bytes, double* ms_out, double* gbps)

@@ -130,32 +130,7 @@ __attribute__((weak)) int profile_run(const mtg_index*, const uint64_t*, size_t,
     set_error("this build has no device code for the profile");
     return MTG_ERR_NO_DEVICE;
 }
-__attribute__((weak)) int find_homo_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, int, mtg_find_call*, size_t, size_t*, int,
-                                        mtg_find_stats*)
-{
-    set_error("this build has no device code for find");
-    return MTG_ERR_NO_DEVICE;
-}
-__attribute__((weak)) int find_del_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, int, mtg_find_call*, size_t, size_t*, int,
-                                       mtg_find_del_stats*)
-{
-    set_error("this build has no device code for find");
-    return MTG_ERR_NO_DEVICE;
-}
-__attribute__((weak)) int find_snp_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, int, mtg_find_call*, size_t, size_t*, int,
-                                       mtg_find_snp_stats*)
-{
-    set_error("this build has no device code for find");
-    return MTG_ERR_NO_DEVICE;
-}
-__attribute__((weak)) int find_msnp_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, int, int, mtg_find_call*, size_t, size_t*,
-                                        mtg_find_msnp_gap*, size_t, size_t*, int, mtg_find_msnp_stats*)
-{
-    set_error("this build has no device code for find");
-    return MTG_ERR_NO_DEVICE;
-}
-__attribute__((weak)) int find_het_run(const mtg_index*, const uint64_t*, size_t, const uint64_t*, const uint32_t*, size_t, const uint64_t*, const uint64_t*, int, int, mtg_find_call*, size_t,
-                                       size_t*, int, mtg_find_het_stats*)
+__attribute__((weak)) int find_run(const mtg_index*, FindLayer, const FindArgs&, void*)
 {
     set_error("this build has no device code for find");
     return MTG_ERR_NO_DEVICE;
@@ -1951,82 +1926,93 @@ static int find_check_args(const mtg_index* idx, bool have_input, int max_repeat
     if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
     return MTG_OK;
 }
+/* what the two multi-SNP entries ask beyond find_check_args: 1 <= snp_min_val <= k, and an array where gap_cap asks for one */
+static int find_msnp_check_args(const mtg_index* idx, const mtgi::FindArgs& a)
+{
+    if (a.gap_cap && !a.gap_recs) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
+    if (a.snp_min_val < 1 || a.snp_min_val > idx->dev.k) { mtgi::set_error("snp_min_val must be 1 .. k"); return MTG_ERR_ARG; }
+    return MTG_OK;
+}
+/* the output side of an entry's arguments; the input is the helper's to fill in */
+static mtgi::FindArgs find_args(int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls, int snp_min_val = 0, mtg_find_msnp_gap* gaps = nullptr, size_t gap_cap = 0,
+                                size_t* n_gaps = nullptr)
+{
+    mtgi::FindArgs a;
+    a.max_repeat = max_repeat; a.calls = calls; a.cap = cap; a.n_calls = n_calls;
+    a.snp_min_val = snp_min_val; a.gap_recs = gaps; a.gap_cap = gap_cap; a.n_gap_recs = n_gaps;
+    return a;
+}
+typedef int (*FindMoreChecks)(const mtg_index*, const mtgi::FindArgs&);
+/* A _sequences entry: the checks (the layer's own behind the common ones), the strings packed, the run.  packed(P, a), where given, sees the
+ * packed input ahead of the run and may add to the arguments.  st: the layer's statistics (find_run) */
+static int find_sequences(const mtg_index* idx, mtgi::FindLayer layer, const char* const* seqs, size_t nseq, mtgi::FindArgs a, void* st, FindMoreChecks more = nullptr,
+                          const std::function<int(const PackedSeqs&, mtgi::FindArgs&)>& packed = nullptr)
+{
+    if (int rc = find_check_args(idx, !nseq || seqs, a.max_repeat, a.calls, a.cap, a.n_calls)) return rc;
+    if (more) { if (int rc = more(idx, a)) return rc; }
+    PackedSeqs P;
+    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, P)) return MTG_ERR_ARG;
+    if (packed) { if (int rc = packed(P, a)) return rc; }
+    a.words = P.words.data(); a.nwords = P.words.size(); a.word_off = P.off.data(); a.len = P.len.data(); a.nseq = nseq; a.bad = P.bad.data();
+    return mtgi::find_run(idx, layer, a, st);
+}
+/* A _packed_device entry: the checks, the run on the caller's device arrays */
+static int find_packed_device(const mtg_index* idx, mtgi::FindLayer layer, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, mtgi::FindArgs a,
+                              void* st, FindMoreChecks more = nullptr)
+{
+    if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), a.max_repeat, a.calls, a.cap, a.n_calls)) return rc;
+    if (more) { if (int rc = more(idx, a)) return rc; }
+    a.words = d_words; a.word_off = d_word_off; a.len = d_len; a.nseq = nseq; a.device_ptrs = 1;
+    return mtgi::find_run(idx, layer, a, st);
+}
 
 int mtg_index_find_homo_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_stats* st)
 {
-    if (int rc = find_check_args(idx, !nseq || seqs, max_repeat, calls, cap, n_calls)) return rc;
-    PackedSeqs P;
-    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, P)) return MTG_ERR_ARG;
-    return mtgi::find_homo_run(idx, P.words.data(), P.words.size(), P.off.data(), P.len.data(), nseq, P.bad.data(), max_repeat, calls, cap, n_calls, 0, st);
+    return find_sequences(idx, mtgi::FIND_HOMO, seqs, nseq, find_args(max_repeat, calls, cap, n_calls), st);
 }
 int mtg_index_find_homo_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
                                       mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_stats* st)
 {
-    if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), max_repeat, d_calls, cap, n_calls)) return rc;
-    return mtgi::find_homo_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, d_calls, cap, n_calls, 1, st);
+    return find_packed_device(idx, mtgi::FIND_HOMO, d_words, d_word_off, d_len, nseq, find_args(max_repeat, d_calls, cap, n_calls), st);
 }
-
 int mtg_index_find_del_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_del_stats* st)
 {
-    if (int rc = find_check_args(idx, !nseq || seqs, max_repeat, calls, cap, n_calls)) return rc;
-    PackedSeqs P;
-    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, P)) return MTG_ERR_ARG;
-    return mtgi::find_del_run(idx, P.words.data(), P.words.size(), P.off.data(), P.len.data(), nseq, P.bad.data(), max_repeat, calls, cap, n_calls, 0, st);
+    return find_sequences(idx, mtgi::FIND_DEL, seqs, nseq, find_args(max_repeat, calls, cap, n_calls), st);
 }
 int mtg_index_find_del_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
                                      mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_del_stats* st)
 {
-    if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), max_repeat, d_calls, cap, n_calls)) return rc;
-    return mtgi::find_del_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, d_calls, cap, n_calls, 1, st);
+    return find_packed_device(idx, mtgi::FIND_DEL, d_words, d_word_off, d_len, nseq, find_args(max_repeat, d_calls, cap, n_calls), st);
 }
-
 int mtg_index_find_snp_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_snp_stats* st)
 {
-    if (int rc = find_check_args(idx, !nseq || seqs, max_repeat, calls, cap, n_calls)) return rc;
-    PackedSeqs P;
-    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, P)) return MTG_ERR_ARG;
-    return mtgi::find_snp_run(idx, P.words.data(), P.words.size(), P.off.data(), P.len.data(), nseq, P.bad.data(), max_repeat, calls, cap, n_calls, 0, st);
+    return find_sequences(idx, mtgi::FIND_SNP, seqs, nseq, find_args(max_repeat, calls, cap, n_calls), st);
 }
 int mtg_index_find_snp_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat,
                                      mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_snp_stats* st)
 {
-    if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), max_repeat, d_calls, cap, n_calls)) return rc;
-    return mtgi::find_snp_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, d_calls, cap, n_calls, 1, st);
-}
-
-/* what the two multi-SNP entries ask beyond find_check_args: 1 <= snp_min_val <= k, and an array where gap_cap asks for one */
-static int find_msnp_check_args(const mtg_index* idx, int snp_min_val, const mtg_find_msnp_gap* gaps, size_t gap_cap)
-{
-    if (gap_cap && !gaps) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
-    if (snp_min_val < 1 || snp_min_val > idx->dev.k) { mtgi::set_error("snp_min_val must be 1 .. k"); return MTG_ERR_ARG; }
-    return MTG_OK;
+    return find_packed_device(idx, mtgi::FIND_SNP, d_words, d_word_off, d_len, nseq, find_args(max_repeat, d_calls, cap, n_calls), st);
 }
 int mtg_index_find_msnp_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, int snp_min_val, mtg_find_call* calls, size_t cap, size_t* n_calls,
                                   mtg_find_msnp_gap* gaps, size_t gap_cap, size_t* n_gaps, mtg_find_msnp_stats* st)
 {
-    if (int rc = find_check_args(idx, !nseq || seqs, max_repeat, calls, cap, n_calls)) return rc;
-    if (int rc = find_msnp_check_args(idx, snp_min_val, gaps, gap_cap)) return rc;
-    PackedSeqs P;
-    if (!pack_with_bad_bits(seqs, nseq, idx->dev.k, nullptr, P)) return MTG_ERR_ARG;
-    return mtgi::find_msnp_run(idx, P.words.data(), P.words.size(), P.off.data(), P.len.data(), nseq, P.bad.data(), max_repeat, snp_min_val, calls, cap, n_calls, gaps, gap_cap, n_gaps, 0, st);
+    return find_sequences(idx, mtgi::FIND_MSNP, seqs, nseq, find_args(max_repeat, calls, cap, n_calls, snp_min_val, gaps, gap_cap, n_gaps), st, find_msnp_check_args);
 }
 int mtg_index_find_msnp_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat, int snp_min_val,
                                       mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_msnp_gap* d_gaps, size_t gap_cap, size_t* n_gaps, mtg_find_msnp_stats* st)
 {
-    if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), max_repeat, d_calls, cap, n_calls)) return rc;
-    if (int rc = find_msnp_check_args(idx, snp_min_val, d_gaps, gap_cap)) return rc;
-    return mtgi::find_msnp_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, max_repeat, snp_min_val, d_calls, cap, n_calls, d_gaps, gap_cap, n_gaps, 1, st);
+    return find_packed_device(idx, mtgi::FIND_MSNP, d_words, d_word_off, d_len, nseq, find_args(max_repeat, d_calls, cap, n_calls, snp_min_val, d_gaps, gap_cap, n_gaps), st, find_msnp_check_args);
 }
 
 int mtg_index_find_het_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, const uint8_t* const* repeated, int max_repeat, int branching_filter, mtg_find_call* calls,
                                  size_t cap, size_t* n_calls, mtg_find_het_stats* st)
 {
-    if (int rc = find_check_args(idx, !nseq || seqs, max_repeat, calls, cap, n_calls)) return rc;
-    const int k = idx->dev.k;
-    PackedSeqs P;
+    mtgi::FindArgs args = find_args(max_repeat, calls, cap, n_calls);
+    args.branching_filter = branching_filter;
     std::vector<uint64_t> rep;
-    if (!pack_with_bad_bits(seqs, nseq, k, nullptr, P)) return MTG_ERR_ARG;
-    if (repeated) { /* the repeat plane: one bit per (k-1)-mer position, at the sequence's word offset */
+    return find_sequences(idx, mtgi::FIND_HET, seqs, nseq, args, st, nullptr, [&](const PackedSeqs& P, mtgi::FindArgs& a) {
+        if (!repeated) return MTG_OK;
+        const int k = idx->dev.k; /* the repeat plane: one bit per (k-1)-mer position, at the sequence's word offset */
         rep.assign(P.words.size(), 0);
         for (size_t s = 0; s < nseq; s++) {
             if (P.len[s] < (uint32_t)k) continue;
@@ -2034,14 +2020,16 @@ int mtg_index_find_het_sequences(const mtg_index* idx, const char* const* seqs, 
             for (uint32_t q = 0; q < P.len[s] - (uint32_t)k + 2u; q++)
                 if (repeated[s][q]) rep[P.off[s] + (q >> 6)] |= 1ull << (q & 63);
         }
-    }
-    return mtgi::find_het_run(idx, P.words.data(), P.words.size(), P.off.data(), P.len.data(), nseq, P.bad.data(), repeated ? rep.data() : nullptr, max_repeat, branching_filter, calls, cap, n_calls, 0, st);
+        a.rep = rep.data();
+        return MTG_OK;
+    });
 }
 int mtg_index_find_het_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, const uint64_t* d_repeat_bits,
                                      int max_repeat, int branching_filter, mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_het_stats* st)
 {
-    if (int rc = find_check_args(idx, !nseq || (d_words && d_word_off && d_len), max_repeat, d_calls, cap, n_calls)) return rc;
-    return mtgi::find_het_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, d_repeat_bits, max_repeat, branching_filter, d_calls, cap, n_calls, 1, st);
+    mtgi::FindArgs args = find_args(max_repeat, d_calls, cap, n_calls);
+    args.branching_filter = branching_filter; args.rep = d_repeat_bits;
+    return find_packed_device(idx, mtgi::FIND_HET, d_words, d_word_off, d_len, nseq, args, st);
 }
 
 int mtg_nw_matches(const char* const* a, const char* const* b, size_t n, uint32_t* matches)

@@ -590,18 +590,25 @@ int scan_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const u
 int profile_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad,
                 const uint64_t* pos_off, uint64_t npos_total, uint32_t* out, mtg_run* runs, size_t runs_cap, size_t* n_runs, int device_ptrs, mtg_profile_stats* st);
 int profile_main(int argc, const char* const* argv);
-/* `find` for homozygous insertions over packed sequences (mtg_gpu_misc.hip): the arrays as for profile_run; calls = host (device_ptrs = 0) or device array */
-int find_homo_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
-                  mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_stats* st);
-int find_del_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
-                 mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_del_stats* st);
-int find_snp_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
-                 mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_snp_stats* st);
-int find_msnp_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, int max_repeat,
-                  int snp_min_val, mtg_find_call* calls, size_t cap, size_t* n_calls, mtg_find_msnp_gap* gap_recs, size_t gap_cap, size_t* n_gap_recs, int device_ptrs,
-                  mtg_find_msnp_stats* st);
-int find_het_run(const mtg_index* idx, const uint64_t* words, size_t nwords, const uint64_t* word_off, const uint32_t* len, size_t nseq, const uint64_t* bad, const uint64_t* rep,
-                 int max_repeat, int branching_filter, mtg_find_call* calls, size_t cap, size_t* n_calls, int device_ptrs, mtg_find_het_stats* st);
+/* `find` over packed sequences (mtg_gpu_misc.hip), one layer a run.  The arrays as for profile_run: device_ptrs = 0: words / word_off / len /
+ * bad / rep are host arrays (bad and rep of nwords words each, rep may be null), calls and gap_recs host memory; 1: all of them device memory
+ * (nwords unused, bad null).  rep and branching_filter are read by FIND_HET alone; snp_min_val and the per-candidate records -- gap_recs of
+ * gap_cap records, may be null, *n_gap_recs (may be null) their total -- by FIND_MSNP alone */
+enum FindLayer { FIND_HOMO, FIND_DEL, FIND_SNP, FIND_MSNP, FIND_HET };
+struct FindArgs {
+    const uint64_t *words = nullptr, *word_off = nullptr;
+    const uint32_t* len = nullptr;
+    size_t nwords = 0, nseq = 0;
+    const uint64_t *bad = nullptr, *rep = nullptr;
+    int max_repeat = 0, branching_filter = 0, snp_min_val = 0;
+    mtg_find_call* calls = nullptr;
+    size_t cap = 0, *n_calls = nullptr;
+    mtg_find_msnp_gap* gap_recs = nullptr;
+    size_t gap_cap = 0, *n_gap_recs = nullptr;
+    int device_ptrs = 0;
+};
+/* stats: the layer's own structure (mtg_find_stats, _del_stats, _snp_stats, _msnp_stats, _het_stats in the order of FindLayer), or null */
+int find_run(const mtg_index* idx, FindLayer layer, const FindArgs& args, void* stats);
 int find_main(int argc, const char* const* argv);
 
 /* The reads of Graph::create as a stream of text blocks: whole sequences separated by '\n' (an invalid character by gatb's rule, so no k-mer

@@ -571,134 +571,109 @@ class Index:
         _check(self.lib.mtg_index_profile_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, pos_off_ptr, out_ptr, runs_ptr, runs_cap, C.byref(total), C.byref(st)))
         return total.value, {f[0]: getattr(st, f[0]) for f in ProfileStats._fields_}
 
-    def find_homo_sequences(self, seqs, max_repeat=5, cap=None):
-        """`find` for homozygous insertions: the insertion sites and the insertions of 1-2 nt of seqs against the graph; returns (calls as a
-        CALL_DTYPE array in the order of the scan, stats dict).  cap: give the array that capacity and return the leading calls
-        (stats["n_calls"] is always the total); by default it is sized to hold them all."""
-        n = len(seqs)
-        arr = (C.c_char_p * n)(*[s.encode() for s in seqs])
-        room = 1024 if cap is None else int(cap)
-        while True:
-            calls = np.zeros(room, dtype=CALL_DTYPE)
-            total, st = C.c_size_t(), FindStats()
-            _check(self.lib.mtg_index_find_homo_sequences(self.h, arr, n, max_repeat, calls.ctypes.data if room else None, room, C.byref(total), C.byref(st)))
-            if cap is not None or total.value <= room:
-                break
-            room = total.value
-        stats = {f[0]: getattr(st, f[0]) for f in FindStats._fields_}
-        stats["n_calls"] = total.value
-        return calls[:min(total.value, room)], stats
-
-    def find_homo_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap):
-        """the same on packed sequences in device memory (pointers as integers; calls_ptr: device array of cap mtg_find_call); returns (total calls, stats dict)"""
-        total, st = C.c_size_t(), FindStats()
-        _check(self.lib.mtg_index_find_homo_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap, C.byref(total), C.byref(st)))
-        return total.value, {f[0]: getattr(st, f[0]) for f in FindStats._fields_}
-
-    def find_del_sequences(self, seqs, max_repeat=5, cap=None):
-        """`find` for homozygous deletions (kind 4: pos = the nucleotide before the deleted text, ins = the deleted length) of seqs against the
-        graph; returns (calls as a CALL_DTYPE array in the order of the scan, stats dict).  cap as in find_homo_sequences."""
-        n = len(seqs)
-        arr = (C.c_char_p * n)(*[s.encode() for s in seqs])
-        room = 1024 if cap is None else int(cap)
-        while True:
-            calls = np.zeros(room, dtype=CALL_DTYPE)
-            total, st = C.c_size_t(), FindDelStats()
-            _check(self.lib.mtg_index_find_del_sequences(self.h, arr, n, max_repeat, calls.ctypes.data if room else None, room, C.byref(total), C.byref(st)))
-            if cap is not None or total.value <= room:
-                break
-            room = total.value
-        stats = {f[0]: getattr(st, f[0]) for f in FindDelStats._fields_}
-        return calls[:min(total.value, room)], stats
-
-    def find_del_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap):
-        """the same on packed sequences in device memory (pointers as integers; calls_ptr: device array of cap mtg_find_call); returns (total calls, stats dict)"""
-        total, st = C.c_size_t(), FindDelStats()
-        _check(self.lib.mtg_index_find_del_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap, C.byref(total), C.byref(st)))
-        return total.value, {f[0]: getattr(st, f[0]) for f in FindDelStats._fields_}
-
-    def find_snp_sequences(self, seqs, max_repeat=5, cap=None):
-        """`find` for isolated homozygous SNPs (kind 5: pos = the SNP's position, ins = ALT's ASCII code | REF's << 8) of seqs against the graph;
-        returns (calls as a CALL_DTYPE array in the order of the scan, stats dict).  cap as in find_homo_sequences."""
-        n = len(seqs)
-        arr = (C.c_char_p * n)(*[s.encode() for s in seqs])
-        room = 1024 if cap is None else int(cap)
-        while True:
-            calls = np.zeros(room, dtype=CALL_DTYPE)
-            total, st = C.c_size_t(), FindSnpStats()
-            _check(self.lib.mtg_index_find_snp_sequences(self.h, arr, n, max_repeat, calls.ctypes.data if room else None, room, C.byref(total), C.byref(st)))
-            if cap is not None or total.value <= room:
-                break
-            room = total.value
-        stats = {f[0]: getattr(st, f[0]) for f in FindSnpStats._fields_[:5]}
-        return calls[:min(total.value, room)], stats
-
-    def find_snp_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap):
-        """the same on packed sequences in device memory (pointers as integers; calls_ptr: device array of cap mtg_find_call); returns (total calls, stats dict)"""
-        total, st = C.c_size_t(), FindSnpStats()
-        _check(self.lib.mtg_index_find_snp_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap, C.byref(total), C.byref(st)))
-        return total.value, {f[0]: getattr(st, f[0]) for f in FindSnpStats._fields_[:5]}
-
-    def find_msnp_sequences(self, seqs, max_repeat=5, snp_min_val=5, cap=None, gaps=True):
-        """`find` for close homozygous SNPs, the forward multi-SNP observer (kind 6: pos = the SNP's position, ins = ALT's ASCII code | REF's << 8,
-        left / right = the gap's two k-mers) of seqs against the graph; returns (calls as a CALL_DTYPE array in the order of the scan, the
-        candidate gaps as a MSNP_GAP_DTYPE array -- None with gaps=False, which passes NULL --, stats dict).  cap as in find_homo_sequences."""
+    def _find_sequences(self, layer, stats_type, seqs, args, cap, gaps=None):
+        """mtg_index_find_<layer>_sequences on seqs, args going between the sequences and the call array.  cap None: the array grows until it
+        holds every call.  gaps not None: the entry has the multi-SNP layer's gap-record array, which grows alike (True) or is passed as NULL
+        (False).  Returns (the leading calls, their total, the gap records or None, the statistics structure)"""
+        fn = getattr(self.lib, "mtg_index_find_%s_sequences" % layer)
         n = len(seqs)
         arr = (C.c_char_p * n)(*[s.encode() for s in seqs])
         room = 1024 if cap is None else int(cap)
         groom = 256 if gaps else 0
         while True:
-            calls = np.zeros(room, dtype=CALL_DTYPE)
-            recs = np.zeros(groom, dtype=MSNP_GAP_DTYPE)
-            total, gtotal, st = C.c_size_t(), C.c_size_t(), FindMsnpStats()
-            _check(self.lib.mtg_index_find_msnp_sequences(self.h, arr, n, max_repeat, snp_min_val, calls.ctypes.data if room else None, room, C.byref(total),
-                                                          recs.ctypes.data if groom else None, groom, C.byref(gtotal) if gaps else None, C.byref(st)))
+            calls, recs = np.zeros(room, dtype=CALL_DTYPE), np.zeros(groom, dtype=MSNP_GAP_DTYPE)
+            total, gtotal, st = C.c_size_t(), C.c_size_t(), stats_type()
+            out = [calls.ctypes.data if room else None, room, C.byref(total)]
+            if gaps is not None:
+                out += [recs.ctypes.data if groom else None, groom, C.byref(gtotal) if gaps else None]
+            _check(fn(self.h, arr, n, *args, *out, C.byref(st)))
             if (cap is not None or total.value <= room) and gtotal.value <= groom:
                 break
             if cap is None:
                 room = max(room, total.value)
             groom = max(groom, gtotal.value)
-        stats = {f[0]: getattr(st, f[0]) for f in FindMsnpStats._fields_}
-        return calls[:min(total.value, room)], (recs[:gtotal.value] if gaps else None), stats
+        return calls[:min(total.value, room)], total.value, (recs[:gtotal.value] if gaps else None), st
+
+    def _find_packed_device(self, layer, stats_type, args, calls_ptr, cap, gaps=None):
+        """mtg_index_find_<layer>_packed_device, args going ahead of the call array; gaps: (gaps_ptr, gap_cap) of the multi-SNP layer.  Returns
+        (total calls, total gap records, the statistics structure)"""
+        total, gtotal, st = C.c_size_t(), C.c_size_t(), stats_type()
+        more = () if gaps is None else (*gaps, C.byref(gtotal))
+        _check(getattr(self.lib, "mtg_index_find_%s_packed_device" % layer)(self.h, *args, calls_ptr, cap, C.byref(total), *more, C.byref(st)))
+        return total.value, gtotal.value, st
+
+    @staticmethod
+    def _find_stats(st, fields=None, n_calls=None):
+        """the statistics dict of a find entry: the leading `fields` fields of the structure (None: all), and n_calls where the structure has none"""
+        stats = {f[0]: getattr(st, f[0]) for f in st._fields_[:fields]}
+        if n_calls is not None:
+            stats["n_calls"] = n_calls
+        return stats
+
+    def find_homo_sequences(self, seqs, max_repeat=5, cap=None):
+        """`find` for homozygous insertions: the insertion sites and the insertions of 1-2 nt of seqs against the graph; returns (calls as a
+        CALL_DTYPE array in the order of the scan, stats dict).  cap: give the array that capacity and return the leading calls
+        (stats["n_calls"] is always the total); by default it is sized to hold them all."""
+        calls, total, _, st = self._find_sequences("homo", FindStats, seqs, (max_repeat,), cap)
+        return calls, self._find_stats(st, n_calls=total)
+
+    def find_homo_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap):
+        """the same on packed sequences in device memory (pointers as integers; calls_ptr: device array of cap mtg_find_call); returns (total calls, stats dict)"""
+        total, _, st = self._find_packed_device("homo", FindStats, (words_ptr, word_off_ptr, len_ptr, nseq, max_repeat), calls_ptr, cap)
+        return total, self._find_stats(st)
+
+    def find_del_sequences(self, seqs, max_repeat=5, cap=None):
+        """`find` for homozygous deletions (kind 4: pos = the nucleotide before the deleted text, ins = the deleted length) of seqs against the
+        graph; returns (calls as a CALL_DTYPE array in the order of the scan, stats dict).  cap as in find_homo_sequences."""
+        calls, _, _, st = self._find_sequences("del", FindDelStats, seqs, (max_repeat,), cap)
+        return calls, self._find_stats(st)
+
+    def find_del_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap):
+        """the same on packed sequences in device memory (pointers as integers; calls_ptr: device array of cap mtg_find_call); returns (total calls, stats dict)"""
+        total, _, st = self._find_packed_device("del", FindDelStats, (words_ptr, word_off_ptr, len_ptr, nseq, max_repeat), calls_ptr, cap)
+        return total, self._find_stats(st)
+
+    def find_snp_sequences(self, seqs, max_repeat=5, cap=None):
+        """`find` for isolated homozygous SNPs (kind 5: pos = the SNP's position, ins = ALT's ASCII code | REF's << 8) of seqs against the graph;
+        returns (calls as a CALL_DTYPE array in the order of the scan, stats dict).  cap as in find_homo_sequences."""
+        calls, _, _, st = self._find_sequences("snp", FindSnpStats, seqs, (max_repeat,), cap)
+        return calls, self._find_stats(st, fields=5)
+
+    def find_snp_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, calls_ptr, cap):
+        """the same on packed sequences in device memory (pointers as integers; calls_ptr: device array of cap mtg_find_call); returns (total calls, stats dict)"""
+        total, _, st = self._find_packed_device("snp", FindSnpStats, (words_ptr, word_off_ptr, len_ptr, nseq, max_repeat), calls_ptr, cap)
+        return total, self._find_stats(st, fields=5)
+
+    def find_msnp_sequences(self, seqs, max_repeat=5, snp_min_val=5, cap=None, gaps=True):
+        """`find` for close homozygous SNPs, the forward multi-SNP observer (kind 6: pos = the SNP's position, ins = ALT's ASCII code | REF's << 8,
+        left / right = the gap's two k-mers) of seqs against the graph; returns (calls as a CALL_DTYPE array in the order of the scan, the
+        candidate gaps as a MSNP_GAP_DTYPE array -- None with gaps=False, which passes NULL --, stats dict).  cap as in find_homo_sequences."""
+        calls, _, recs, st = self._find_sequences("msnp", FindMsnpStats, seqs, (max_repeat, snp_min_val), cap, gaps=bool(gaps))
+        return calls, recs, self._find_stats(st)
 
     def find_msnp_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, snp_min_val, calls_ptr, cap, gaps_ptr=None, gap_cap=0):
         """the same on packed sequences in device memory (pointers as integers; calls_ptr: device array of cap mtg_find_call, gaps_ptr: device array
         of gap_cap mtg_find_msnp_gap or None); returns (total calls, total candidate gaps, stats dict)"""
-        total, gtotal, st = C.c_size_t(), C.c_size_t(), FindMsnpStats()
-        _check(self.lib.mtg_index_find_msnp_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, snp_min_val, calls_ptr, cap, C.byref(total), gaps_ptr, gap_cap,
-                                                          C.byref(gtotal), C.byref(st)))
-        return total.value, gtotal.value, {f[0]: getattr(st, f[0]) for f in FindMsnpStats._fields_}
+        total, gtotal, st = self._find_packed_device("msnp", FindMsnpStats, (words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, snp_min_val), calls_ptr, cap, gaps=(gaps_ptr, gap_cap))
+        return total, gtotal, self._find_stats(st)
 
     def find_het_sequences(self, seqs, repeated=None, max_repeat=5, branching_filter=15, cap=None):
         """`find` for heterozygous insertions: the sites (kind 2) and the insertions of 1-2 nt (kind 3) of seqs against the graph; returns (calls
         as a CALL_DTYPE array in the order of the scan, stats dict).  repeated: per sequence a uint8 array of len - k + 2 flags, one per
         (k-1)-mer position (what scan_sequences of an index of k - 1 returns), or None: nothing is repeated.  branching_filter < 0: no filter.
         cap as in find_homo_sequences."""
-        n = len(seqs)
-        arr = (C.c_char_p * n)(*[s.encode() for s in seqs])
         rep = keep = None
         if repeated is not None:
             keep = [np.ascontiguousarray(r, dtype=np.uint8) for r in repeated]
-            rep = (C.c_void_p * n)(*[r.ctypes.data if r.size else None for r in keep])
-        room = 1024 if cap is None else int(cap)
-        while True:
-            calls = np.zeros(room, dtype=CALL_DTYPE)
-            total, st = C.c_size_t(), FindHetStats()
-            _check(self.lib.mtg_index_find_het_sequences(self.h, arr, n, rep, max_repeat, branching_filter, calls.ctypes.data if room else None, room, C.byref(total), C.byref(st)))
-            if cap is not None or total.value <= room:
-                break
-            room = total.value
-        stats = {f[0]: getattr(st, f[0]) for f in FindHetStats._fields_}
-        stats["n_calls"] = total.value
-        return calls[:min(total.value, room)], stats
+            rep = (C.c_void_p * len(seqs))(*[r.ctypes.data if r.size else None for r in keep])
+        calls, total, _, st = self._find_sequences("het", FindHetStats, seqs, (rep, max_repeat, branching_filter), cap)
+        return calls, self._find_stats(st, n_calls=total)
 
     def find_het_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, repeat_bits_ptr, max_repeat, branching_filter, calls_ptr, cap):
         """the same on packed sequences in device memory (pointers as integers; repeat_bits_ptr: the repeat plane in the layout of
         scan_packed_device's output for an index of k - 1, or None; calls_ptr: device array of cap mtg_find_call); returns (total calls, stats dict)"""
-        total, st = C.c_size_t(), FindHetStats()
-        _check(self.lib.mtg_index_find_het_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, repeat_bits_ptr, max_repeat, branching_filter, calls_ptr, cap, C.byref(total),
-                                                         C.byref(st)))
-        return total.value, {f[0]: getattr(st, f[0]) for f in FindHetStats._fields_}
+        total, _, st = self._find_packed_device("het", FindHetStats, (words_ptr, word_off_ptr, len_ptr, nseq, repeat_bits_ptr, max_repeat, branching_filter), calls_ptr, cap)
+        return total, self._find_stats(st)
 
     def stage_a(self, sources, targets, params=None):
         """Contigs of every gap (gatb IterativeExtensions::construct_linear_seqs, src/Filler.cpp:884)."""

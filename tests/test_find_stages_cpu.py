@@ -1,5 +1,5 @@
 """The inputs of tests/find_stage_cases.py are the stages they are named after: the plain models alone (tests/find_cases.py,
-tests/find_del_cases.py, tests/find_het_cases.py), no device.  tests/test_gpu_find_stages.py runs the same inputs through the library."""
+tests/find_del_cases.py, tests/find_snp_cases.py, tests/find_msnp_cases.py, tests/find_het_cases.py), no device.  tests/test_gpu_find_stages.py runs the same inputs through the library."""
 import pytest
 
 from tests import find_stage_cases as sc
@@ -11,6 +11,8 @@ def test_every_layer_has_every_stage_within_the_size_limits():
         for stage, seqs in sc.STAGES[layer].items():
             assert len(seqs) <= 4 and all(len(s) <= 200 for s in seqs), (layer, stage)
     assert len(sc.ALL_LAYERS) <= 4 and all(len(s) <= 200 for s in sc.ALL_LAYERS)
+    assert len(sc.UNJUDGED) == 1 and 200 < len(sc.UNJUDGED[0]) <= 320
+    assert set(sc.inputs("msnp")) == set(sc.STAGE_NAMES) | {"unjudged"} and all(sc.inputs(layer) is sc.STAGES[layer] for layer in sc.LAYERS if layer != "msnp")
 
 
 @pytest.mark.parametrize("layer", sc.LAYERS)
@@ -34,20 +36,48 @@ def test_each_input_is_the_stage_it_claims(layer):
     else:
         assert st["n_gaps"] > 0
         lengths = [n for _, _, n, fresh in sc.fc.gaps_by_anchors(sc.SOLID, k, inputs["unseen"]) if fresh]
-        assert lengths and all(n > k - 1 if layer == "homo" else n < k - sc.MAX_REPEAT for n in lengths)
+        if layer == "snp":
+            assert lengths and all(n != k for n in lengths)
+        elif layer == "msnp":
+            assert lengths and all(n <= k + sc.SNP_MIN_VAL for n in lengths)
+        else:
+            assert lengths and all(n > k - 1 if layer == "homo" else n < k - sc.MAX_REPEAT for n in lengths)
 
     calls, st = res["uncalled"]
     assert calls == [] and st["n_candidates"] > 0 and st[seen] > 0
     assert not any(v for key, v in st.items() if key not in ("n_gaps", "n_candidates"))
 
     calls, st = res["calls"]
+    if layer == "msnp":   # several calls per gap
+        recs = sc.msnp_gap_records(sc.SOLID, inputs["calls"])
+        assert len(calls) >= 3 and st["n_candidates"] == len(recs) == 2 and [r[2:] for r in recs] == [(k + 7, k + 7, 2), (k + 9, k + 9, 2)]
+        assert {c[2] for c in calls} == {6} and st["n_calls"] == len(calls) and st["n_full"] == 2
+        return
     assert len(calls) >= 3 and st["n_candidates"] >= len(calls)
-    if layer == "homo":
+    if layer == "snp":
+        assert {c[2] for c in calls} == {5} and sorted(c[0] for c in calls) == [0, 1, 2] and st["n_calls"] == 3
+    elif layer == "homo":
         assert {c[2] for c in calls} == {0, 1} and {c[3] for c in calls} == {0, 2}
     elif layer == "del":
         assert {c[2] for c in calls} == {4} and sorted(c[6] for c in calls) == [5, 20, 40] and st["n_calls"] == 3
     else:
         assert {c[2] for c in calls} == {2, 3} and {c[3] for c in calls} == {0, 2}
+
+
+def test_the_unjudged_input_has_a_candidate_and_nothing_to_list():
+    """one candidate gap of 255 positions or more and no other candidate: counted in n_long, consumed 0, no call, no slab"""
+    calls, st = sc.model("msnp", sc.SOLID, sc.UNJUDGED)
+    recs = sc.msnp_gap_records(sc.SOLID, sc.UNJUDGED)
+    assert calls == [] and len(recs) == 1 and recs[0][2] >= 255 and recs[0][3:] == (0, 0)
+    assert st["n_candidates"] == 1 and st["n_long"] == 1 and not any(st[x] for x in ("n_calls", "n_full", "n_partial"))
+    # the uncalled input is the other way round: judged, and stopped at its first step
+    recs = sc.msnp_gap_records(sc.SOLID, sc.STAGES["msnp"]["uncalled"])
+    assert len(recs) == 1 and k_plus(recs[0][2]) and recs[0][3:] == (0, 0)
+
+
+def k_plus(length):
+    """a gap the multi-SNP observer judges: longer than k + snp_min_val, shorter than 255"""
+    return sc.K + sc.SNP_MIN_VAL < length < 255
 
 
 def test_every_layer_calls_on_the_shared_input():
