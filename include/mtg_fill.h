@@ -229,7 +229,7 @@ int mtg_index_find_del_packed_device(const mtg_index* idx, const uint64_t* d_wor
  * its k k-mers are those that cover the position g = start + k - 1.  With ref the nucleotide at g, the call is the first of the other three
  * nucleotides in the order A, C, T, G for which all k k-mers, g replaced by it, are in the graph; with none there is no call.  The observer
  * leaves the scan alone.  (In the reference a call also corrects the k-mer history that the heterozygous observer reads: not done, the
- * heterozygous entry knows nothing of these calls.)  FindMultiSNP, which takes the longer gaps, is mtg_index_find_msnp_sequences; FindMultiSNPrev is not built.  Records as above:
+ * heterozygous entry knows nothing of these calls.)  FindMultiSNP, which takes the longer gaps, is mtg_index_find_msnp_sequences; FindMultiSNPrev is mtg_index_find_msnp_rev_sequences.  Records as above:
  *   kind   5 SNP
  *   pos    g, 0-based (the VCF's POS is pos + 1);  repeat = 0
  *   left, right   start - 1 and start + k, the positions of the two k-mers
@@ -261,7 +261,7 @@ int mtg_index_find_snp_packed_device(const mtg_index* idx, const uint64_t* d_wor
  * other entries know nothing of these calls.)  DEVIATION: the reference keeps the text in a ring of 256 k-mers addressed by unsigned char;
  * from L = 255 on the ring has been overwritten and the reference reports positions it did not look at (23 of 29 such gaps of a random
  * set differ from the rule above).  Gaps of 255 positions and more are not judged: counted in n_long, no call.  FindMultiSNPrev, which
- * walks a gap from the right, is not built.  Records as above:
+ * walks a gap from the right, is mtg_index_find_msnp_rev_sequences below.  Records as above:
  *   kind   6 SNP of a multi-SNP gap (its VCF line is that of kind 5)
  *   pos    g, 0-based;  repeat = 0
  *   left, right   start - 1 and start + L, the positions of the gap's two k-mers, the same for every SNP of the gap
@@ -283,6 +283,42 @@ int mtg_index_find_msnp_sequences(const mtg_index* idx, const char* const* seqs,
 /* same on 2-bit packed sequences already in DEVICE memory (no invalid positions); d_calls and d_gaps are device arrays */
 int mtg_index_find_msnp_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat, int snp_min_val,
                                       mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_msnp_gap* d_gaps, size_t gap_cap, size_t* n_gaps, mtg_find_msnp_stats* st);
+
+/* The same with the reverse pass: the reference's FindMultiSNPrev (src/FindSNP.hpp:593-709 with snp_at_begin, :219-293), which it asks right
+ * behind FindMultiSNP.  passes: 1 = the forward pass alone (calls, statistics and the first five record fields of
+ * mtg_index_find_msnp_sequences, bit for bit), 2 = the reverse pass alone, 3 = forward, then reverse on what is left; anything else is
+ * MTG_ERR_ARG.  With c what the forward pass consumed (0 when it is not run), the reverse pass is asked only if c != L and
+ * L - c > k + snp_min_val, the reference's own entry test on the shrunken gap.  It works on the residual gap start' = start + c, L' = L - c,
+ * on the same private text T with the forward substitutions in place, with a cursor d = 0; while d != L':
+ *   q = start + L - 1 - d, ref = T[q]; for each of the other three nucleotides a, f(a) = the number of leading windows j = 0, 1, ..
+ *   < min(k, L' - d + 1) in the graph, window j being the k-mer of T at q - j with q (its nucleotide j) replaced by a.  Window j = L' - d is
+ *   the k-mer at start' - 1, the left anchor, and it decides: if it holds, M = L' - d + 1 and the chain stops without a call; if it fails,
+ *   M = L' - d and the gap is taken whole.  M = max f and the winner as in the forward pass.  M < snp_min_val: stop.  d + M > L': stop.  Else
+ *   a SNP at q, REF ref, ALT the winner; T[q] = winner; d += M.
+ * consumed_rev = the final d.  The gap is full if c + d = L, partial if 0 < c + d < L: n_full and n_partial go by c + d, n_calls counts both
+ * passes.  The reverse pass reads the text [start - 1, start + L + k - 1), one nucleotide to the left of the forward text.
+ * DEVIATIONS: gaps of 255 positions and more are judged by neither pass (n_long, consumed 0, no call), as above.  THE RING INDICES COUNT AS
+ * RESTORED AFTER A GAP: after a partial take the reference subtracts the consumed length from m_position, m_het_kmer_end_index and
+ * m_het_kmer_begin_index (:672-674) and restores m_position alone (src/FindBreakpoints.hpp:441-446), so its ring is addressed shifted from
+ * then on; a gap that starts exactly two positions behind a gap the reverse pass took in part reads a stale left anchor there (reverse pass
+ * alone: 1 of 1 200 random cases differs, one with such a pair of gaps; forward then reverse: none).  The rule here is
+ * the pure function of the gap.  (A gap taken in part would reach the deletion and insertion observers shortened on both sides and with a
+ * corrected kmer_end: not done.)  Records as above, and
+ *   kind   7 SNP of the reverse pass (its VCF line is that of kind 5)
+ *   pos    q, 0-based;  repeat = 0
+ *   left, right   start + c - 1 and start + L, the two k-mers of the residual gap
+ *   ins    as for kind 5
+ * in the order of the scan; the calls of one gap in the order they are made: the forward ones ascending, then the reverse ones DESCENDING in
+ * pos.  Everything else as for mtg_index_find_msnp_sequences. */
+typedef struct mtg_find_msnp_rev_gap {
+    uint32_t seq, start, length, consumed, n_snps, consumed_rev, n_snps_rev;
+} mtg_find_msnp_rev_gap;
+int mtg_index_find_msnp_rev_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, int snp_min_val, int passes, mtg_find_call* calls, size_t cap,
+                                      size_t* n_calls, mtg_find_msnp_rev_gap* gaps, size_t gap_cap, size_t* n_gaps, mtg_find_msnp_stats* st);
+/* same on 2-bit packed sequences already in DEVICE memory (no invalid positions); d_calls and d_gaps are device arrays */
+int mtg_index_find_msnp_rev_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat, int snp_min_val,
+                                          int passes, mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_msnp_rev_gap* d_gaps, size_t gap_cap, size_t* n_gaps,
+                                          mtg_find_msnp_stats* st);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Gap filling = Filler::gapFillFromSource over a batch of gaps.
@@ -562,7 +598,8 @@ int mtg_fill_main_on_index(mtg_index* idx, int argc, const char* const* argv);
  * and prefix.profile.txt, the statistics as `key : value` lines.  Returns 0 / 1; nothing is written unless the whole profile succeeded. */
 int mtg_profile_main(int argc, const char* const* argv);
 /* `MindTheGap find (-in reads | -graph container) -ref genome.fa (-homo-insertions | -hete-only | -insert-only | -deletion-only | -homo-only
- * -no-snp | -no-snp | -solo-snps | -homo-only -solo-snps | -multi-snps [-snp-min-val 5] | -solo-snps -multi-snps [-snp-min-val 5]) [-max-rep 5] [-het-max-occ 1] [-branching-filter 15] [-kmer-size -abundance-min -abundance-max] [-out prefix]`: the part
+ * -no-snp | -no-snp | -solo-snps | -homo-only -solo-snps | -multi-snps [-snp-min-val 5] | -solo-snps -multi-snps [-snp-min-val 5] |
+ * [-solo-snps] [-multi-snps] -rev-snps [-snp-min-val 5]) [-max-rep 5] [-het-max-occ 1] [-branching-filter 15] [-kmer-size -abundance-min -abundance-max] [-out prefix]`: the part
  * of the reference's `find` that mtg_index_find_homo_sequences (-homo-insertions), mtg_index_find_het_sequences plus the homozygous insertions
  * of 1-2 nt (-hete-only, as the reference's option of that name) or both in full (-insert-only, calls merged in detection order) cover, and with
  * mtg_index_find_del_sequences the reference's -deletion-only (deletions and the homozygous insertions of 1-2 nt), -homo-only -no-snp (those and
@@ -573,9 +610,12 @@ int mtg_profile_main(int argc, const char* const* argv);
  * anything that runs the heterozygous observer.  -multi-snps (mtg_index_find_msnp_sequences alone) and -solo-snps -multi-snps (both forward SNP
  * observers, their lists merged in detection order) are not configurations of the reference either; with any flag that runs the deletion, the
  * insertion or the heterozygous observers they are refused: a partially consumed gap would reach those shortened and with a corrected kmer_begin,
- * which is not built.  A SNP is one VCF line of writeVcfVariant's form (TYPE=SNP;LEN=1;FUZZY=0).  The repeat flags of the heterozygous
+ * which is not built.  -rev-snps (mtg_index_find_msnp_rev_sequences with passes 2), -multi-snps -rev-snps (passes 3) and either with -solo-snps
+ * are configurations of this tool alone as well; the calls of one gap keep the order in which they are made (forward ascending, then reverse
+ * descending), and with the same flags they are refused with a message of their own: the gap would reach the later observers with a
+ * corrected kmer_end too.  A SNP is one VCF line of writeVcfVariant's form (TYPE=SNP;LEN=1;FUZZY=0).  The repeat flags of the heterozygous
  * observer come from an index of the genome file at k - 1 with abundance_min = het_max_occ + 1 (k >= 12).  Any other combination of these flags
- * stops with a message that names what is not built (the reverse multi-SNP observer, -snp-only, the default find, -bed) and returns 1.  Writes prefix.breakpoints (writeBreakpoint,
+ * stops with a message that names what is not built (-snp-only, the default find, -bed) and returns 1.  Writes prefix.breakpoints (writeBreakpoint,
  * src/FindBreakpoints.hpp:640-658) and prefix.othervariants.vcf (header of src/Finder.cpp:513-541, records of writeIndel and, for deletions,
  * writeVcfVariant: REF = the genome's text from pos over del_size + 1 characters as it stands, ALT its first); ids bkptN count
  * from 1 in detection order across both files; the REPEATED field stays empty (the reference fills it from a Bloom filter of the genome's

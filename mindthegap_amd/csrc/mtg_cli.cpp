@@ -1465,16 +1465,18 @@ template <typename Entry> static int find_all_calls(std::vector<mtg_find_call>& 
  * homozygous deletions of mtg_index_find_del_sequences ahead of the insertion observers.  `-solo-snps | -homo-only -solo-snps`, configurations of
  * this tool alone: the isolated homozygous SNPs of mtg_index_find_snp_sequences, alone or ahead of the deletion and the homozygous insertion
  * observers.  `-multi-snps | -solo-snps -multi-snps`, also of this tool alone: the close homozygous SNPs of mtg_index_find_msnp_sequences (the
- * forward multi-SNP observer), alone or with the isolated ones; with any other observer they are refused.  Both files are written once the whole
- * scan is there. */
+ * forward multi-SNP observer), alone or with the isolated ones; with any other observer they are refused.  `-rev-snps | -multi-snps -rev-snps`,
+ * each also with -solo-snps, of this tool alone as well: the reverse multi-SNP pass of mtg_index_find_msnp_rev_sequences, alone (passes 2) or
+ * behind the forward one (passes 3).  Both files are written once the whole scan is there. */
 int find_main(int argc, const char* const* argv)
 {
     std::string in, graph, ref, out = "MindTheGap_Expe"; /* the reference names it after the date (src/Finder.cpp: MindTheGap_Expe-<date>) */
     int k = 31, abundance_min = -1, abundance_max = 0, max_repeat = 5, het_max_occ = 1, branching_filter = 15, snp_min_val = 5;
     bool homo_flag = false, hete_only = false, insert_only = false, deletion_only = false, homo_only = false, no_snp = false, other_mode = false, solo_snps = false;
-    bool multi_snps = false, min_val_given = false;
+    bool multi_snps = false, rev_snps = false, min_val_given = false;
     const char* usage = "Usage: MindTheGap find (-in <reads> | -graph <container>) -ref <genome.fa> (-homo-insertions | -hete-only | -insert-only | -deletion-only | -homo-only -no-snp | "
-                        "-no-snp | -solo-snps | -homo-only -solo-snps | -multi-snps [-snp-min-val 5] | -solo-snps -multi-snps [-snp-min-val 5]) [-max-rep 5] [-het-max-occ 1] "
+                        "-no-snp | -solo-snps | -homo-only -solo-snps | -multi-snps [-snp-min-val 5] | -solo-snps -multi-snps [-snp-min-val 5] | [-solo-snps] [-multi-snps] -rev-snps [-snp-min-val 5]) "
+                        "[-max-rep 5] [-het-max-occ 1] "
                         "[-branching-filter 15] [-kmer-size 31] [-abundance-min auto] [-abundance-max 0] [-out <prefix>]\n";
     for (int i = 0; i < argc; i++) {
         const std::string a = argv[i];
@@ -1493,6 +1495,7 @@ int find_main(int argc, const char* const* argv)
         else if (a == "-no-snp") no_snp = true;
         else if (a == "-solo-snps") solo_snps = true;
         else if (a == "-multi-snps") multi_snps = true;
+        else if (a == "-rev-snps") rev_snps = true;
         else if (a == "-snp-min-val") { ok = val(v); snp_min_val = atoi(v.c_str()); min_val_given = true; }
         else if (a == "-snp-only" || a == "-no-insert" || a == "-no-deletion" || a == "-no-hetero" || a == "-with-backup") other_mode = true; /* refused below, with the message */
         else if (a == "-het-max-occ") { ok = val(v); het_max_occ = atoi(v.c_str()); }
@@ -1519,6 +1522,16 @@ int find_main(int argc, const char* const* argv)
     /* -multi-snps, not an option of the reference either: the close SNPs of FindMultiSNP alone, or with -solo-snps both forward SNP observers
      * (their candidates are disjoint: L = k against L > k + snp_min_val).  Never with an observer that the reference asks after it: a gap
      * taken in part reaches those shortened and with a corrected kmer_begin, which is not built */
+    /* -rev-snps, not an option of the reference either: the reverse pass of FindMultiSNPrev alone, or with -multi-snps behind the forward pass on
+     * what that one left, either with -solo-snps.  Never with an observer that the reference asks after it: a gap taken in part reaches those
+     * shortened on its right side too and with a corrected kmer_end, which is not built */
+    if (rev_snps && (other_mode || ins_flags || del_flags)) {
+        fprintf(stderr, "EXCEPTION: -rev-snps (the close homozygous SNPs of the reverse multi-SNP observer, not an option of the reference) runs alone, as -multi-snps -rev-snps, or "
+                        "either of these with -solo-snps.  With a flag that runs the deletion, insertion or heterozygous observers (-homo-only, -deletion-only, -no-snp, "
+                        "-homo-insertions, -hete-only, -insert-only) it is refused: a partially consumed gap reaches the later observers shortened and with a corrected kmer_begin "
+                        "and, now, a corrected kmer_end, and that is not built.  -snp-only and the default find are not built either.\n%s", usage);
+        return 1;
+    }
     if (multi_snps && (other_mode || ins_flags || del_flags)) {
         fprintf(stderr, "EXCEPTION: -multi-snps (the close homozygous SNPs of the forward multi-SNP observer, not an option of the reference) runs alone or as -solo-snps -multi-snps.  "
                         "With a flag that runs the deletion, insertion or heterozygous observers (-homo-only, -deletion-only, -no-snp, -homo-insertions, -hete-only, -insert-only) it is "
@@ -1526,9 +1539,10 @@ int find_main(int argc, const char* const* argv)
                         "observer, -snp-only and the default find are not built either.\n%s", usage);
         return 1;
     }
-    if (min_val_given && !multi_snps) { fprintf(stderr, "EXCEPTION: -snp-min-val is accepted with -multi-snps only\n%s", usage); return 1; }
-    if (multi_snps && snp_min_val < 1) { fprintf(stderr, "EXCEPTION: -snp-min-val must be 1 .. k\n"); return 1; }
-    const bool run_multi = multi_snps;
+    if (min_val_given && !multi_snps && !rev_snps) { fprintf(stderr, "EXCEPTION: -snp-min-val is accepted with -multi-snps only\n%s", usage); return 1; }
+    if ((multi_snps || rev_snps) && snp_min_val < 1) { fprintf(stderr, "EXCEPTION: -snp-min-val must be 1 .. k\n"); return 1; }
+    const bool run_multi = multi_snps || rev_snps;
+    const int passes = (multi_snps ? 1 : 0) | (rev_snps ? 2 : 0);
     const bool solo_alone = solo_snps && !other_mode && !ins_flags && !del_flags, solo_homo = solo_snps && !other_mode && !ins_flags && homo_only && !deletion_only && !no_snp;
     const bool run_snp = solo_alone || solo_homo;
     if (solo_snps && !run_snp) {
@@ -1584,6 +1598,7 @@ int find_main(int argc, const char* const* argv)
     }
     if (run_multi && !rc) {
         rc = find_all_calls(msnp_calls, n_msnp, [&](mtg_find_call* c, size_t cap, size_t* n) {
+            if (rev_snps) return mtg_index_find_msnp_rev_sequences(idx, seqs.data(), seqs.size(), max_repeat, snp_min_val, passes, c, cap, n, nullptr, 0, nullptr, nullptr);
             return mtg_index_find_msnp_sequences(idx, seqs.data(), seqs.size(), max_repeat, snp_min_val, c, cap, n, nullptr, 0, nullptr, nullptr);
         });
     }
@@ -1611,7 +1626,8 @@ int find_main(int argc, const char* const* argv)
     if (rc) { fprintf(stderr, "EXCEPTION: %s\n", mtg_last_error()); return 1; }
     if (run_multi) {
         /* both forward SNP observers are asked at right + 1 of their gap and no gap is a candidate of both: the lists, each in scan order, merge by
-         * (seq, right) into the order of detection; the SNPs of one gap stay together, ascending.  The merged list takes the place of the solo calls */
+         * (seq, right) into the order of detection; the SNPs of one gap stay together in the order of their list -- the forward ones ascending, then
+         * the reverse ones descending -- and are not sorted by pos.  The merged list takes the place of the solo calls */
         std::vector<mtg_find_call> both;
         both.reserve(n_snp + n_msnp);
         size_t i = 0, j = 0;
@@ -1692,7 +1708,7 @@ int find_main(int argc, const char* const* argv)
         const std::string left = kmer_string(s, c.left);
         const int id = (int)i + 1;
         const bool het = c.kind == 2 || c.kind == 3;
-        if (c.kind == 5 || c.kind == 6) { /* writeVcfVariant as FindSNP.hpp:340-347 and :502-510 call it: REF and ALT from the 2-bit codes, upper case */
+        if (c.kind == 5 || c.kind == 6 || c.kind == 7) { /* writeVcfVariant as FindSNP.hpp:340-347 and :502-510 call it: REF and ALT from the 2-bit codes, upper case */
             appendf(vcf, "%s\t%lli\tbkpt%i\t%c\t%c\t.\tPASS\tTYPE=SNP;LEN=1;FUZZY=0\tGT\t1/1\n", name.c_str(), (long long)c.pos + 1, id, (int)((c.ins >> 8) & 0xFFu), (int)(c.ins & 0xFFu));
         } else if (c.kind == 4) { /* writeVcfVariant, :661-678, as FindDeletion.hpp:148-160 calls it: the genome's text as it stands */
             const std::string del = s.substr(c.pos, (size_t)c.ins + 1);
@@ -1721,7 +1737,7 @@ int find_main(int argc, const char* const* argv)
     printf("    Breakpoint detection options\n        max_repeat                               : %i\n", max_repeat);
     if (run_het) printf("        hetero_max_occ                           : %i\n        branching filter value                   : %i\n", het_max_occ, branching_filter);
     printf("        homo_insertions                          : %s\n        hete_insertions                          : %s\n        snp                                      : %s\n"
-           "        deletion                                 : %s\n", homo_sites ? "yes" : "no", run_het ? "yes" : "no", run_multi ? (run_snp ? "isolated and close (forward)" : "close only (forward)") : run_snp ? "isolated only" : "no", run_del ? "yes" : "no");
+           "        deletion                                 : %s\n", homo_sites ? "yes" : "no", run_het ? "yes" : "no", run_multi ? (passes == 1 ? (run_snp ? "isolated and close (forward)" : "close only (forward)") : passes == 2 ? (run_snp ? "isolated and close (reverse)" : "close only (reverse)") : (run_snp ? "isolated and close (forward, then reverse)" : "close only (forward, then reverse)")) : run_snp ? "isolated only" : "no", run_del ? "yes" : "no");
     printf("Results\n    Insertion breakpoints\n        homozygous                               : %llu\n            clean                                    : %llu\n"
            "            fuzzy                                    : %llu\n", (unsigned long long)(st.n_homo_clean + st.n_homo_fuzzy), (unsigned long long)st.n_homo_clean, (unsigned long long)st.n_homo_fuzzy);
     if (run_het) printf("        heterozygous                             : %llu\n            clean                                    : %llu\n            fuzzy                                    : %llu\n",

@@ -864,6 +864,95 @@ __global__ void __launch_bounds__(FIND_WAVES * 64) k_msnp_judge(Index ix, const 
         if (at) atomicAdd(&counters[at == L ? CNT_MSNP_FULL : CNT_MSNP_PARTIAL], 1ull);
     }
 }
+/* The three counts of one step of either pass (the kernel below): lane l holds km, the k-mer of its window j = l % 32 (mine: j < cap).  Lanes
+ * 0-31 the first alternative in A, C, T, G order, lanes 32-63 the second, then lanes 0-31 the third; a count is the leading ones of its
+ * half of the ballot.  REV: the window replaces the k-mer's nucleotide j (msnp_rev_window), else its nucleotide k - 1 - j (snp_window) */
+template <bool REV>
+__device__ __forceinline__ void msnp_step_counts(const Index& ix, uint64_t km, bool mine, uint32_t j, uint32_t half, uint32_t ref, uint32_t& lines, uint32_t& f0, uint32_t& f1, uint32_t& f2)
+{
+    const int k = ix.k;
+    const uint64_t cmpl = 0xAAAAAAAAAAAAAAAAULL & kmask(k);
+    for (uint32_t it = 0; it < 2u; it++) {
+        bool solid = false;
+        if (mine && 2u * it + half < 3u) {
+            const uint32_t a = snp_alt(ref, 2u * it + half);
+            Kmer x;
+            x.r = (REV ? msnp_rev_window(km, j, a) : snp_window(km, (int)j, k, a)) ^ cmpl;
+            x.f = revcomp(x.r, k);
+            solid = bloom_test(ix.bloom, x, k) && abundance(ix, x, lines) != 0;
+        }
+        const unsigned long long bal = __ballot(solid);
+        if (it == 0) { f0 = msnp_leading((uint32_t)bal); f1 = msnp_leading((uint32_t)(bal >> 32)); }
+        else f2 = msnp_leading((uint32_t)bal);
+    }
+}
+/* The observer with the reverse pass (mtg_find_msnp.h: msnp_passes_chain), one wave per candidate as k_msnp_judge, which stays as it is for
+ * the forward-only entries.  The private copy is the text [start - 1, start + L + k): the at most MSNP_TEXT_WORDS words from (start - 1) / 32
+ * on, word i in a register of lane i; start - 1 >= 0 and start + L + k - 1 lie in the sequence (both k-mers are anchors), no other word is
+ * read.  passes & 1: the forward chain as in k_msnp_judge, `start` now at rel0 + 1.  passes & 2, if msnp_rev_is_asked on what is left: the
+ * reverse chain on the SAME register copy.  A step at cursor d fetches the three words that hold [q - (cap - 1), q + k) by uniform lane
+ * reads; lane l takes window j = l % 32 (< cap) of the k-mer at q - j, window cap - 1 = L' - d being the left anchor's k-mer at
+ * start' - 1.  Winner and stop tests are msnp_winner / msnp_stop, uniform in the wave; lane 0 appends the entry behind the forward ones, the
+ * lane that holds q substitutes.  out[4c ..] = consumed, calls, consumed_rev, calls of the reverse pass.  CNT_MSNP_FULL / _PARTIAL by
+ * consumed + consumed_rev, CNT_MSNP_LONG as in k_msnp_judge */
+__global__ void __launch_bounds__(FIND_WAVES * 64) k_msnp_rev_judge(Index ix, const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off, const mtg_run* __restrict__ gaps,
+                                                                    const uint32_t* __restrict__ cand, uint64_t ncand, int m, int passes, const uint64_t* __restrict__ slab_off, uint32_t* slab,
+                                                                    uint32_t* out, unsigned long long* counters)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t c = (uint64_t)blockIdx.x * FIND_WAVES + (threadIdx.x >> 6);
+    if (c >= ncand) return; /* (uniform in the wave; the kernel has no workgroup barrier) */
+    const mtg_run g = gaps[cand[c]];
+    const uint32_t L = g.length;
+    if (!msnp_is_judged(L)) {
+        if (lane == 0) { out[4 * c] = 0u; out[4 * c + 1] = 0u; out[4 * c + 2] = 0u; out[4 * c + 3] = 0u; atomicAdd(&counters[CNT_MSNP_LONG], 1ull); }
+        return;
+    }
+    const int k = ix.k;
+    const uint32_t nw = msnp_rev_text_words(g.start, L, k), rel0 = msnp_rev_rel0(g.start);
+    uint64_t tw = lane < nw ? words[word_off[g.seq] + ((g.start - 1u) >> 5) + lane] : 0ull;
+    uint32_t* entries = slab + slab_off[c];
+    const uint32_t half = lane >> 5, j = lane & 31u;
+    uint32_t lines = 0, at = 0, n = 0, d = 0, nr = 0;
+    while ((passes & MSNP_PASS_FWD) && at != L) {
+        const uint32_t rel = rel0 + 1u + at, w0 = rel >> 5, r = rel & 31u, cap = msnp_cap(L, at, k);
+        const uint64_t t0 = msnp_lane_word(tw, w0), t1 = msnp_lane_word(tw, w0 + 1u), t2 = msnp_lane_word(tw, w0 + 2u);
+        const uint32_t ref = (uint32_t)(snp_text_kmer(t0, t1, t2, r, k) >> (2 * (k - 1))) & 3u;
+        const bool mine = j < cap;
+        const uint64_t km = mine ? snp_text_kmer(t0, t1, t2, r + j, k) : 0ull;
+        uint32_t f0 = 0, f1 = 0, f2 = 0, best;
+        msnp_step_counts<false>(ix, km, mine, j, half, ref, lines, f0, f1, f2);
+        const uint32_t alt = snp_alt(ref, msnp_winner(f0, f1, f2, k, &best));
+        if (msnp_stop(at, best, L, m)) break;
+        if (lane == 0) entries[n] = msnp_entry(at, alt, ref);
+        n++;
+        const uint32_t gp = rel + (uint32_t)k - 1u;
+        if (lane == (gp >> 5)) tw = msnp_substituted(tw, gp, alt);
+        at += best;
+    }
+    if ((passes & MSNP_PASS_REV) && msnp_rev_is_asked(L, at, k, m)) {
+        const uint32_t left = L - at;
+        while (d != left) {
+            const uint32_t q = rel0 + L - d, cap = msnp_cap(left, d, k), w0 = (q - (cap - 1u)) >> 5, base = w0 << 5; /* q - base <= cap - 1 + 31 <= 62 */
+            const uint64_t t0 = msnp_lane_word(tw, w0), t1 = msnp_lane_word(tw, w0 + 1u), t2 = msnp_lane_word(tw, w0 + 2u);
+            const uint32_t ref = (uint32_t)snp_text_kmer(t0, t1, t2, q - base, k) & 3u;
+            const bool mine = j < cap;
+            const uint64_t km = mine ? snp_text_kmer(t0, t1, t2, q - j - base, k) : 0ull;
+            uint32_t f0 = 0, f1 = 0, f2 = 0, best;
+            msnp_step_counts<true>(ix, km, mine, j, half, ref, lines, f0, f1, f2);
+            const uint32_t alt = snp_alt(ref, msnp_winner(f0, f1, f2, k, &best));
+            if (msnp_stop(d, best, left, m)) break;
+            if (lane == 0) entries[n + nr] = msnp_rev_entry(d, alt, ref);
+            nr++;
+            if (lane == (q >> 5)) tw = msnp_substituted(tw, q, alt);
+            d += best;
+        }
+    }
+    if (lane == 0) {
+        out[4 * c] = at; out[4 * c + 1] = n; out[4 * c + 2] = d; out[4 * c + 3] = nr;
+        if (at + d) atomicAdd(&counters[at + d == L ? CNT_MSNP_FULL : CNT_MSNP_PARTIAL], 1ull);
+    }
+}
 /* the gap of slab entry e: the last candidate whose slab begins at or before e (a candidate without room shares its offset with the next) */
 __device__ __forceinline__ uint64_t msnp_owner(const uint64_t* __restrict__ slab_off, uint64_t ncand, uint64_t e)
 {
@@ -896,8 +985,35 @@ __global__ void __launch_bounds__(RUNS_BLOCK) k_msnp_gaps(const mtg_run* __restr
     q.seq = g.seq; q.start = g.start; q.length = g.length; q.consumed = out[2 * c]; q.n_snps = out[2 * c + 1];
     recs[c] = q;
 }
+/* the same two for the entries with the reverse pass (out: four words per candidate, k_msnp_rev_judge).  A reverse entry is kind 7:
+ * pos = q, left = the k-mer before the residual gap, start + consumed - 1 */
+__global__ void __launch_bounds__(RUNS_BLOCK) k_msnp_rev_emit(const mtg_run* __restrict__ gaps, const uint32_t* __restrict__ cand, uint64_t ncand, const uint64_t* __restrict__ slab_off,
+                                                              const uint32_t* __restrict__ slab, const uint32_t* __restrict__ out, const uint32_t* __restrict__ sel, uint64_t n, int k,
+                                                              mtg_find_call* calls)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t e = sel[j], o = slab[e];
+    const uint64_t c = msnp_owner(slab_off, ncand, e);
+    const mtg_run g = gaps[cand[c]];
+    const bool rev = msnp_entry_is_rev(o);
+    mtg_find_call q;
+    q.seq = g.seq; q.pos = rev ? msnp_rev_pos_of(g.start, g.length, o) : msnp_pos_of(g.start, o, k); q.kind = rev ? 7u : 6u; q.repeat = 0u;
+    q.left = g.start - 1u + (rev ? out[4 * c] : 0u); q.right = g.start + g.length; q.ins = snp_ins_of(o);
+    calls[j] = q;
+}
+__global__ void __launch_bounds__(RUNS_BLOCK) k_msnp_rev_gaps(const mtg_run* __restrict__ gaps, const uint32_t* __restrict__ cand, const uint32_t* __restrict__ out, uint64_t n,
+                                                              mtg_find_msnp_rev_gap* recs)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    if (c >= n) return;
+    const mtg_run g = gaps[cand[c]];
+    mtg_find_msnp_rev_gap q;
+    q.seq = g.seq; q.start = g.start; q.length = g.length; q.consumed = out[4 * c]; q.n_snps = out[4 * c + 1]; q.consumed_rev = out[4 * c + 2]; q.n_snps_rev = out[4 * c + 3];
+    recs[c] = q;
+}
 /* the gap observer of the close homozygous SNPs: gap_is_msnp_candidate (mtg_find_msnp.h) on snp_min_val, the slab middle (calls, with the
- * stage of the find runs further down), kind 6 */
+ * stage of the find runs further down), kind 6; MultiRevObserver: the same with the passes of FindArgs, kinds 6 and 7 */
 struct MultiObserver {
     using Stats = mtg_find_msnp_stats;
     static int candidate_param(int, int snp_min_val) { return snp_min_val; }
@@ -908,6 +1024,9 @@ struct MultiObserver {
         st.n_positions = c[CNT_POSITIONS]; st.n_gaps = c[CNT_GAPS_SEEN]; st.n_candidates = n_cand; st.n_calls = total;
         st.n_full = c[CNT_MSNP_FULL]; st.n_partial = c[CNT_MSNP_PARTIAL]; st.n_long = c[CNT_MSNP_LONG];
     }
+};
+struct MultiRevObserver : MultiObserver {
+    static int calls(FindStage& S, const FindArgs& a, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand, uint64_t* total);
 };
 
 /* ---- `find` for heterozygous insertions (include/mtg_fill.h: mtg_index_find_het_sequences; the rule and the word-level logic: mtg_find_het.h).
@@ -1540,13 +1659,16 @@ int OneCallPerGap<Observer>::calls(FindStage& S, const FindArgs& a, const mtg_ru
 
 /* The multi-SNP observer's calls, several per gap: a slab of L / m entries per candidate; the chain, one wave per candidate; the per-candidate
  * records (the first a.gap_cap of them, where a.gap_recs is given); the calls listed from the slabs and written.  Without a slab -- every
- * candidate unjudged -- there is nothing to list, and the span ends by end_tail */
-int MultiObserver::calls(FindStage& S, const FindArgs& a, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand, uint64_t* total)
+ * candidate unjudged -- there is nothing to list, and the span ends by end_tail.  REV: the entries with the reverse pass -- k_msnp_rev_judge
+ * on a.passes, four result words per candidate, records of mtg_find_msnp_rev_gap */
+template <bool REV>
+static int msnp_calls(FindStage& S, const FindArgs& a, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand, uint64_t* total)
 {
+    using Rec = typename std::conditional<REV, mtg_find_msnp_rev_gap, mtg_find_msnp_gap>::type;
     const SeqInput& in = S.in;
     DevBuf d_bound, d_slab_off, d_slab, d_out, d_recs;
-    const unsigned nb = (unsigned)((n_cand + RUNS_BLOCK - 1) / RUNS_BLOCK);
-    HIP_TRY(d_bound.alloc((size_t)n_cand * 4)); HIP_TRY(d_slab_off.alloc((size_t)n_cand * 8)); HIP_TRY(d_out.alloc((size_t)n_cand * 8));
+    const unsigned nb = (unsigned)((n_cand + RUNS_BLOCK - 1) / RUNS_BLOCK), judge_blocks = (unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES);
+    HIP_TRY(d_bound.alloc((size_t)n_cand * 4)); HIP_TRY(d_slab_off.alloc((size_t)n_cand * 8)); HIP_TRY(d_out.alloc((size_t)n_cand * (REV ? 16 : 8)));
     HIP_TRY(hipEventRecord(S.e_tail[0], 0));
     hipLaunchKernelGGL(k_msnp_bound, dim3(nb), dim3(RUNS_BLOCK), 0, 0, gaps, cand, n_cand, a.snp_min_val, d_bound.as<uint32_t>());
     hipLaunchKernelGGL(k_profile_seq_scan, dim3(1), dim3(1024), 0, 0, d_bound.as<uint32_t>(), (size_t)n_cand, d_slab_off.as<uint64_t>(), S.cnt() + CNT_GAP_CALLS);
@@ -1556,23 +1678,35 @@ int MultiObserver::calls(FindStage& S, const FindArgs& a, const mtg_run* gaps, c
     if (n_slab > 0xFFFFFFFFull) { set_error("more than 2^32 - 1 possible SNPs in the candidate gaps"); return MTG_ERR_ARG; }
     HIP_TRY(d_slab.alloc((size_t)n_slab * 4));
     if (n_slab) HIP_TRY(hipMemsetAsync(d_slab.p, 0, (size_t)n_slab * 4, 0));
-    hipLaunchKernelGGL(k_msnp_judge, dim3((unsigned)((n_cand + FIND_WAVES - 1) / FIND_WAVES)), dim3(FIND_WAVES * 64), 0, 0, S.idx->dev, in.words, in.word_off, gaps, cand, n_cand, a.snp_min_val,
-                       d_slab_off.as<uint64_t>(), d_slab.as<uint32_t>(), d_out.as<uint32_t>(), S.cnt());
+    if constexpr (REV)
+        hipLaunchKernelGGL(k_msnp_rev_judge, dim3(judge_blocks), dim3(FIND_WAVES * 64), 0, 0, S.idx->dev, in.words, in.word_off, gaps, cand, n_cand, a.snp_min_val, a.passes,
+                           d_slab_off.as<uint64_t>(), d_slab.as<uint32_t>(), d_out.as<uint32_t>(), S.cnt());
+    else
+        hipLaunchKernelGGL(k_msnp_judge, dim3(judge_blocks), dim3(FIND_WAVES * 64), 0, 0, S.idx->dev, in.words, in.word_off, gaps, cand, n_cand, a.snp_min_val,
+                           d_slab_off.as<uint64_t>(), d_slab.as<uint32_t>(), d_out.as<uint32_t>(), S.cnt());
     const uint64_t keep_recs = a.gap_recs ? std::min<uint64_t>(n_cand, a.gap_cap) : 0;
-    mtg_find_msnp_gap* pr = a.gap_recs;
+    Rec* pr = static_cast<Rec*>(a.gap_recs);
     if (keep_recs) {
-        if (!a.device_ptrs) { HIP_TRY(d_recs.alloc((size_t)keep_recs * sizeof(mtg_find_msnp_gap))); pr = d_recs.as<mtg_find_msnp_gap>(); }
-        hipLaunchKernelGGL(k_msnp_gaps, dim3((unsigned)((keep_recs + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, gaps, cand, d_out.as<uint32_t>(), keep_recs, pr);
+        if (!a.device_ptrs) { HIP_TRY(d_recs.alloc((size_t)keep_recs * sizeof(Rec))); pr = d_recs.as<Rec>(); }
+        const dim3 rec_blocks((unsigned)((keep_recs + RUNS_BLOCK - 1) / RUNS_BLOCK));
+        if constexpr (REV) hipLaunchKernelGGL(k_msnp_rev_gaps, rec_blocks, dim3(RUNS_BLOCK), 0, 0, gaps, cand, d_out.as<uint32_t>(), keep_recs, pr);
+        else hipLaunchKernelGGL(k_msnp_gaps, rec_blocks, dim3(RUNS_BLOCK), 0, 0, gaps, cand, d_out.as<uint32_t>(), keep_recs, pr);
     }
     if (n_slab) {
         if (int rc = S.calls_tail(d_slab.as<uint32_t>(), n_slab, CNT_GAP_CALLS, a.calls, a.cap, total, [&](const uint32_t* sel, uint64_t keep, mtg_find_call* out) {
-                hipLaunchKernelGGL(k_msnp_emit, dim3((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK)), dim3(RUNS_BLOCK), 0, 0, gaps, cand, n_cand, d_slab_off.as<uint64_t>(), d_slab.as<uint32_t>(), sel, keep,
-                                   S.k, out);
+                const dim3 emit_blocks((unsigned)((keep + RUNS_BLOCK - 1) / RUNS_BLOCK));
+                if constexpr (REV)
+                    hipLaunchKernelGGL(k_msnp_rev_emit, emit_blocks, dim3(RUNS_BLOCK), 0, 0, gaps, cand, n_cand, d_slab_off.as<uint64_t>(), d_slab.as<uint32_t>(), d_out.as<uint32_t>(), sel, keep,
+                                       S.k, out);
+                else
+                    hipLaunchKernelGGL(k_msnp_emit, emit_blocks, dim3(RUNS_BLOCK), 0, 0, gaps, cand, n_cand, d_slab_off.as<uint64_t>(), d_slab.as<uint32_t>(), sel, keep, S.k, out);
             })) return rc;
     } else if (int rc = S.end_tail()) return rc;
-    if (keep_recs && !a.device_ptrs) HIP_TRY(hipMemcpy(a.gap_recs, pr, (size_t)keep_recs * sizeof(mtg_find_msnp_gap), hipMemcpyDeviceToHost));
+    if (keep_recs && !a.device_ptrs) HIP_TRY(hipMemcpy(a.gap_recs, pr, (size_t)keep_recs * sizeof(Rec), hipMemcpyDeviceToHost));
     return MTG_OK;
 }
+int MultiObserver::calls(FindStage& S, const FindArgs& a, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand, uint64_t* total) { return msnp_calls<false>(S, a, gaps, cand, n_cand, total); }
+int MultiRevObserver::calls(FindStage& S, const FindArgs& a, const mtg_run* gaps, const uint32_t* cand, uint64_t n_cand, uint64_t* total) { return msnp_calls<true>(S, a, gaps, cand, n_cand, total); }
 
 /* `find` by a gap observer over packed sequences: what all of them share.  Between "there are candidates" and "the calls are written" the
  * observer is on its own (Observer::calls) */
@@ -1657,7 +1791,7 @@ static int find_het_run(const mtg_index* idx, const FindArgs& a, mtg_find_het_st
     return MTG_OK;
 }
 
-/* The one run entry behind the ten find entries of the ABI; the only place where the statistics pointer gets its type back: the layer's run
+/* The one run entry behind the twelve find entries of the ABI; the only place where the statistics pointer gets its type back: the layer's run
  * says which */
 template <typename Stats>
 static int find_run_as(int (*run)(const mtg_index*, const FindArgs&, Stats*), const mtg_index* idx, const FindArgs& a, void* stats)
@@ -1671,6 +1805,7 @@ int find_run(const mtg_index* idx, FindLayer layer, const FindArgs& args, void* 
         case FIND_DEL: return find_run_as(find_gap_run<DelObserver>, idx, args, stats);
         case FIND_SNP: return find_run_as(find_gap_run<SoloObserver>, idx, args, stats);
         case FIND_MSNP: return find_run_as(find_gap_run<MultiObserver>, idx, args, stats);
+        case FIND_MSNP_REV: return find_run_as(find_gap_run<MultiRevObserver>, idx, args, stats);
         case FIND_HET: return find_run_as(find_het_run, idx, args, stats);
     }
     set_error("invalid argument");

@@ -1919,22 +1919,23 @@ int mtg_index_profile_packed_device(const mtg_index* idx, const uint64_t* d_word
     return mtgi::profile_run(idx, d_words, 0, d_word_off, d_len, nseq, nullptr, d_pos_off, 0, d_out, d_runs, runs_cap, n_runs, 1, st);
 }
 
-/* the argument checks of the ten find entries; have_input: the input arrays that nseq asks for are there */
+/* the argument checks of the twelve find entries; have_input: the input arrays that nseq asks for are there */
 static int find_check_args(const mtg_index* idx, bool have_input, int max_repeat, const mtg_find_call* calls, size_t cap, const size_t* n_calls)
 {
     if (!idx || !n_calls || !have_input || (cap && !calls)) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
     if (max_repeat < 0) { mtgi::set_error("max_repeat must not be negative"); return MTG_ERR_ARG; }
     return MTG_OK;
 }
-/* what the two multi-SNP entries ask beyond find_check_args: 1 <= snp_min_val <= k, and an array where gap_cap asks for one */
+/* what the four multi-SNP entries ask beyond find_check_args: 1 <= snp_min_val <= k, an array where gap_cap asks for one, passes 1 .. 3 */
 static int find_msnp_check_args(const mtg_index* idx, const mtgi::FindArgs& a)
 {
     if (a.gap_cap && !a.gap_recs) { mtgi::set_error("null argument"); return MTG_ERR_ARG; }
     if (a.snp_min_val < 1 || a.snp_min_val > idx->dev.k) { mtgi::set_error("snp_min_val must be 1 .. k"); return MTG_ERR_ARG; }
+    if (a.passes < 1 || a.passes > 3) { mtgi::set_error("passes must be 1 (forward), 2 (reverse) or 3 (forward, then reverse)"); return MTG_ERR_ARG; }
     return MTG_OK;
 }
 /* the output side of an entry's arguments; the input is the helper's to fill in */
-static mtgi::FindArgs find_args(int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls, int snp_min_val = 0, mtg_find_msnp_gap* gaps = nullptr, size_t gap_cap = 0,
+static mtgi::FindArgs find_args(int max_repeat, mtg_find_call* calls, size_t cap, size_t* n_calls, int snp_min_val = 0, void* gaps = nullptr, size_t gap_cap = 0,
                                 size_t* n_gaps = nullptr)
 {
     mtgi::FindArgs a;
@@ -2002,6 +2003,24 @@ int mtg_index_find_msnp_packed_device(const mtg_index* idx, const uint64_t* d_wo
                                       mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_msnp_gap* d_gaps, size_t gap_cap, size_t* n_gaps, mtg_find_msnp_stats* st)
 {
     return find_packed_device(idx, mtgi::FIND_MSNP, d_words, d_word_off, d_len, nseq, find_args(max_repeat, d_calls, cap, n_calls, snp_min_val, d_gaps, gap_cap, n_gaps), st, find_msnp_check_args);
+}
+/* the two entries with the reverse pass: the arguments of the two above and the passes, which the other entries leave at 1 */
+static mtgi::FindArgs find_rev_args(mtgi::FindArgs a, int passes)
+{
+    a.passes = passes;
+    return a;
+}
+int mtg_index_find_msnp_rev_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, int max_repeat, int snp_min_val, int passes, mtg_find_call* calls, size_t cap,
+                                      size_t* n_calls, mtg_find_msnp_rev_gap* gaps, size_t gap_cap, size_t* n_gaps, mtg_find_msnp_stats* st)
+{
+    return find_sequences(idx, mtgi::FIND_MSNP_REV, seqs, nseq, find_rev_args(find_args(max_repeat, calls, cap, n_calls, snp_min_val, gaps, gap_cap, n_gaps), passes), st, find_msnp_check_args);
+}
+int mtg_index_find_msnp_rev_packed_device(const mtg_index* idx, const uint64_t* d_words, const uint64_t* d_word_off, const uint32_t* d_len, size_t nseq, int max_repeat, int snp_min_val,
+                                          int passes, mtg_find_call* d_calls, size_t cap, size_t* n_calls, mtg_find_msnp_rev_gap* d_gaps, size_t gap_cap, size_t* n_gaps,
+                                          mtg_find_msnp_stats* st)
+{
+    return find_packed_device(idx, mtgi::FIND_MSNP_REV, d_words, d_word_off, d_len, nseq, find_rev_args(find_args(max_repeat, d_calls, cap, n_calls, snp_min_val, d_gaps, gap_cap, n_gaps), passes),
+                              st, find_msnp_check_args);
 }
 
 int mtg_index_find_het_sequences(const mtg_index* idx, const char* const* seqs, size_t nseq, const uint8_t* const* repeated, int max_repeat, int branching_filter, mtg_find_call* calls,

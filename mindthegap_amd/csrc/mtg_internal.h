@@ -593,21 +593,23 @@ int profile_main(int argc, const char* const* argv);
 /* `find` over packed sequences (mtg_gpu_misc.hip), one layer a run.  The arrays as for profile_run: device_ptrs = 0: words / word_off / len /
  * bad / rep are host arrays (bad and rep of nwords words each, rep may be null), calls and gap_recs host memory; 1: all of them device memory
  * (nwords unused, bad null).  rep and branching_filter are read by FIND_HET alone; snp_min_val and the per-candidate records -- gap_recs of
- * gap_cap records, may be null, *n_gap_recs (may be null) their total -- by FIND_MSNP alone */
-enum FindLayer { FIND_HOMO, FIND_DEL, FIND_SNP, FIND_MSNP, FIND_HET };
+ * gap_cap records, may be null, *n_gap_recs (may be null) their total -- by FIND_MSNP and FIND_MSNP_REV alone.  FIND_MSNP_REV: the multi-SNP
+ * layer as the entries with the reverse pass see it: passes (1 forward, 2 reverse, 3 forward then reverse; the other layers leave it at 1)
+ * and records of mtg_find_msnp_rev_gap where FIND_MSNP has mtg_find_msnp_gap */
+enum FindLayer { FIND_HOMO, FIND_DEL, FIND_SNP, FIND_MSNP, FIND_HET, FIND_MSNP_REV };
 struct FindArgs {
     const uint64_t *words = nullptr, *word_off = nullptr;
     const uint32_t* len = nullptr;
     size_t nwords = 0, nseq = 0;
     const uint64_t *bad = nullptr, *rep = nullptr;
-    int max_repeat = 0, branching_filter = 0, snp_min_val = 0;
+    int max_repeat = 0, branching_filter = 0, snp_min_val = 0, passes = 1;
     mtg_find_call* calls = nullptr;
     size_t cap = 0, *n_calls = nullptr;
-    mtg_find_msnp_gap* gap_recs = nullptr;
+    void* gap_recs = nullptr; /* the layer's record type */
     size_t gap_cap = 0, *n_gap_recs = nullptr;
     int device_ptrs = 0;
 };
-/* stats: the layer's own structure (mtg_find_stats, _del_stats, _snp_stats, _msnp_stats, _het_stats in the order of FindLayer), or null */
+/* stats: the layer's own structure (mtg_find_stats, _del_stats, _snp_stats, _msnp_stats, _het_stats, _msnp_stats in the order of FindLayer), or null */
 int find_run(const mtg_index* idx, FindLayer layer, const FindArgs& args, void* stats);
 int find_main(int argc, const char* const* argv);
 

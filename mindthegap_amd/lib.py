@@ -124,6 +124,8 @@ class FindMsnpStats(C.Structure):
 
 # a candidate gap of the multi-SNP observer (mtg_find_msnp_gap): consumed = length: taken, 0 < consumed < length: in part, 0: untouched
 MSNP_GAP_DTYPE = np.dtype([("seq", np.uint32), ("start", np.uint32), ("length", np.uint32), ("consumed", np.uint32), ("n_snps", np.uint32)])
+# the same of the entries with the reverse pass (mtg_find_msnp_rev_gap): the gap is taken if consumed + consumed_rev = length
+MSNP_REV_GAP_DTYPE = np.dtype(MSNP_GAP_DTYPE.descr + [("consumed_rev", np.uint32), ("n_snps_rev", np.uint32)])
 
 # a call of `find` (mtg_find_call): kind 0 = homozygous insertion site, 1 = homozygous insertion of 1-2 nt, 2 = heterozygous site,
 # 3 = heterozygous insertion of 1-2 nt, 4 = homozygous deletion, 5 = isolated homozygous SNP, 6 = SNP of a multi-SNP gap; ins indexes
@@ -247,6 +249,10 @@ def _bind(lib):
                                                   P(FindMsnpStats)]
     lib.mtg_index_find_msnp_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), C.c_void_p,
                                                       C.c_size_t, P(C.c_size_t), P(FindMsnpStats)]
+    lib.mtg_index_find_msnp_rev_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), C.c_void_p, C.c_size_t,
+                                                      P(C.c_size_t), P(FindMsnpStats)]
+    lib.mtg_index_find_msnp_rev_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t),
+                                                          C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindMsnpStats)]
     lib.mtg_index_find_het_sequences.argtypes = [C.c_void_p, P(C.c_char_p), C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t), P(FindHetStats)]
     lib.mtg_index_find_het_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t),
                                                      P(FindHetStats)]
@@ -571,17 +577,17 @@ class Index:
         _check(self.lib.mtg_index_profile_packed_device(self.h, words_ptr, word_off_ptr, len_ptr, nseq, pos_off_ptr, out_ptr, runs_ptr, runs_cap, C.byref(total), C.byref(st)))
         return total.value, {f[0]: getattr(st, f[0]) for f in ProfileStats._fields_}
 
-    def _find_sequences(self, layer, stats_type, seqs, args, cap, gaps=None):
+    def _find_sequences(self, layer, stats_type, seqs, args, cap, gaps=None, gap_dtype=MSNP_GAP_DTYPE):
         """mtg_index_find_<layer>_sequences on seqs, args going between the sequences and the call array.  cap None: the array grows until it
-        holds every call.  gaps not None: the entry has the multi-SNP layer's gap-record array, which grows alike (True) or is passed as NULL
-        (False).  Returns (the leading calls, their total, the gap records or None, the statistics structure)"""
+        holds every call.  gaps not None: the entry has the multi-SNP layer's gap-record array of gap_dtype, which grows alike (True) or is
+        passed as NULL (False).  Returns (the leading calls, their total, the gap records or None, the statistics structure)"""
         fn = getattr(self.lib, "mtg_index_find_%s_sequences" % layer)
         n = len(seqs)
         arr = (C.c_char_p * n)(*[s.encode() for s in seqs])
         room = 1024 if cap is None else int(cap)
         groom = 256 if gaps else 0
         while True:
-            calls, recs = np.zeros(room, dtype=CALL_DTYPE), np.zeros(groom, dtype=MSNP_GAP_DTYPE)
+            calls, recs = np.zeros(room, dtype=CALL_DTYPE), np.zeros(groom, dtype=gap_dtype)
             total, gtotal, st = C.c_size_t(), C.c_size_t(), stats_type()
             out = [calls.ctypes.data if room else None, room, C.byref(total)]
             if gaps is not None:
@@ -655,6 +661,21 @@ class Index:
         """the same on packed sequences in device memory (pointers as integers; calls_ptr: device array of cap mtg_find_call, gaps_ptr: device array
         of gap_cap mtg_find_msnp_gap or None); returns (total calls, total candidate gaps, stats dict)"""
         total, gtotal, st = self._find_packed_device("msnp", FindMsnpStats, (words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, snp_min_val), calls_ptr, cap, gaps=(gaps_ptr, gap_cap))
+        return total, gtotal, self._find_stats(st)
+
+    def find_msnp_rev_sequences(self, seqs, max_repeat=5, snp_min_val=5, passes=3, cap=None, gaps=True):
+        """`find` for close homozygous SNPs with the reverse pass: passes 1 = forward (find_msnp_sequences), 2 = reverse, 3 = forward, then reverse
+        on what is left.  Kind 6 as there; kind 7, a call of the reverse pass: pos = the SNP's position, left = the k-mer before the residual gap.
+        The calls of one gap in the order they are made: forward ascending, then reverse descending.  Returns (calls, the candidate gaps as a
+        MSNP_REV_GAP_DTYPE array or None, stats dict) as find_msnp_sequences does."""
+        calls, _, recs, st = self._find_sequences("msnp_rev", FindMsnpStats, seqs, (max_repeat, snp_min_val, passes), cap, gaps=bool(gaps), gap_dtype=MSNP_REV_GAP_DTYPE)
+        return calls, recs, self._find_stats(st)
+
+    def find_msnp_rev_packed_device(self, words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, snp_min_val, passes, calls_ptr, cap, gaps_ptr=None, gap_cap=0):
+        """the same on packed sequences in device memory (pointers as integers; calls_ptr: device array of cap mtg_find_call, gaps_ptr: device array
+        of gap_cap mtg_find_msnp_rev_gap or None); returns (total calls, total candidate gaps, stats dict)"""
+        total, gtotal, st = self._find_packed_device("msnp_rev", FindMsnpStats, (words_ptr, word_off_ptr, len_ptr, nseq, max_repeat, snp_min_val, passes), calls_ptr, cap,
+                                                     gaps=(gaps_ptr, gap_cap))
         return total, gtotal, self._find_stats(st)
 
     def find_het_sequences(self, seqs, repeated=None, max_repeat=5, branching_filter=15, cap=None):
